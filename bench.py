@@ -2,6 +2,7 @@
 """bench.py — rays/sec (+ PSNR vs the CPU oracle) of the NeRFactor per-ray rendering hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--legs nerf,nerfactor_microfacet,nerfactor]
+                    [--dump-outputs DIR]
 
 BASELINE.json's metric is "rays/sec (64 samples/ray, 512 light dirs) + PSNR vs TF ref"; one run times, back to back,
 
@@ -104,6 +105,42 @@ def timed(step, steps, warmup, barrier):
         out = step(k)
     barrier()
     return time.perf_counter() - t0, out
+
+
+# --dump-outputs DIR: what each timed path returned in its LAST timed step, as DIR/<leg>_<name>.npy (float32, float64 kept),
+# written by rank 0 after the line.  The headline frame is kept whole; every other output keeps a fixed seeded sample of
+# DUMP_ROWS rows (points / rays), the same rows in every run, so that two builds can be compared array for array.
+DUMP = False
+DUMP_ROWS = 4096
+DUMP_MAX_BYTES = 64 << 20
+OUTPUTS = {}
+
+
+def keep_output(name, x, all_rows=False):
+    """Copy `x` (a tensor, an array or a dict of them -> name_<key>) to the host for dump_outputs; outside the timed region."""
+    if not DUMP:
+        return
+    if isinstance(x, dict):
+        for k, v in x.items():
+            keep_output('%s_%s' % (name, k), v, all_rows)
+        return
+    x = x.detach() if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x))
+    if not all_rows and x.ndim and x.shape[0] > DUMP_ROWS:       # (rows picked on the device: no full-size copy to the host)
+        rows = np.sort(np.random.default_rng(0).choice(x.shape[0], DUMP_ROWS, replace=False))
+        x = x[torch.from_numpy(rows).to(x.device)]
+    x = x.double() if x.dtype == torch.float64 else x.float()
+    OUTPUTS[name] = np.ascontiguousarray(x.cpu().numpy())
+
+
+def dump_outputs(out_dir, outputs=None):
+    outputs = OUTPUTS if outputs is None else outputs
+    total = sum(a.nbytes for a in outputs.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes over the %d-byte budget" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return sorted(outputs)
 
 
 # ------------------------------------------------------------------------------------------------ NeRF leg
@@ -288,6 +325,7 @@ def nerf_leg(args, ops, dev, rank, world, barrier, max_over_ranks):
                          args.steps, args.warmup, barrier)
     elapsed = max_over_ranks(elapsed)
     assert torch.isfinite(rgb).all()
+    keep_output('nerf_rgb', rgb, all_rows=True)
 
     # dominant kernel: the fused NeRF MLP (two launches per view: coarse + fine), HIP events on the launch stream
     n_local = sh.hi - sh.lo
@@ -572,6 +610,7 @@ def nerfactor_leg(name, args, ops, dev, rank, world, barrier, max_over_ranks):
         kt.on = False
     elapsed = max_over_ranks(elapsed)
     assert torch.isfinite(pred['rgb_probes']).all()
+    keep_output(name, pred)
     fg_per_call = n_fg_local / sh.n_views
     lvis_s = kt.mean_ms('lvis_fwd') * 1e-3
     lvis_tf = fg_per_call * N_LIGHTS * 2 * LVIS_MAC / lvis_s / 1e12
@@ -730,6 +769,7 @@ def train_leg(name, args, ops, dev, rank, world, barrier, max_over_ranks):
             ": " + errors[0] if errors else " (not this one)")}
     losses = torch.stack(losses).cpu().numpy()
     assert np.isfinite(losses).all(), "non-finite training loss in the timed steps"
+    keep_output('train_%s_losses' % name, losses)         # the loss of every timed eager step, the last one included
     dt_eager = elapsed / steps
     # One process, foreground-tagged batch: the step as ONE hipGraph replay (optim.GraphedTrainStep = ini key
     # `hip_graph = true`; bit-identical to the eager step, tests/test_gpu_train.py).  The eager NeRFactor step issues
@@ -978,6 +1018,7 @@ def geometry_leg(args, ops, dev, rank, world, barrier, max_over_ranks):
         kt.on = False
         elapsed = max_over_ranks(elapsed)
         occu, depth, normal = state['out']
+        keep_output('geometry', {'occu': occu, 'depth': depth, 'normal': normal})
         fwd_ms, grad_ms = kt.all_ms('nerf_sigma_fwd'), kt.all_ms('nerf_sigma_grad')
     kernel_ms = (sum(fwd_ms) + sum(grad_ms)) / steps
     n_local = sh.hi - sh.lo
@@ -1014,6 +1055,7 @@ def geometry_leg(args, ops, dev, rank, world, barrier, max_over_ranks):
         kt.on = False
         elapsed_l = max_over_ranks(elapsed_l)
         lvis_kernel_ms = sum(kt.all_ms('nerf_sigma_fwd'))
+    keep_output('geometry_lvis', lv['lvis'])
     lxyz, _ = G.gen_light_xyz(16, 32)
     lx = torch.as_tensor(lxyz.reshape(-1, 3).astype(np.float32), device=dev)
     s2l = torch.nn.functional.normalize(lx[None] - surf[:, None], dim=2, eps=1e-12)
@@ -1114,12 +1156,13 @@ def olat_leg(args, ops, dev, rank, world, barrier, max_over_ranks):
             kt.on = k is not None
             out = None
             for b in batches:
-                out = model(b, mode='test', relight_olat=True)[0]['rgb_olat'][:1]
+                out = model(b, mode='test', relight_olat=True)[0]['rgb_olat']
             return out
         elapsed, out = timed(step, args.steps, args.warmup, barrier)
         kt.on = False
     elapsed = max_over_ranks(elapsed)
-    assert torch.isfinite(out).all()
+    assert torch.isfinite(out[:1]).all()
+    keep_output('olat_rgb_olat', out[:, ::8])         # (every 8th of the 512 lights: 3 MB)
     fg_per_call = n_fg_local / sh.n_views
     k_s = kt.mean_ms('shade_olat_fwd') * 1e-3
     # algorithmic bytes: 512 x 12 B written per foreground point; read: the point's visibility row (2 KiB) + 52 B
@@ -1184,6 +1227,7 @@ def relight_sweep_leg(args, ops, dev, rank, world, barrier, max_over_ranks):
     elapsed, out = timed(step, steps, min(args.warmup, 2), barrier)
     elapsed = max_over_ranks(elapsed)
     assert torch.isfinite(out).all() and out.shape[1] == N_PROBES
+    keep_output('relight_rgb_probes', out)
     return {
         "workload": "nerfactor_microfacet relighting sweep (BASELINE.json configs[4]): %d test views x %d novel "
                     "environment maps per step, 800x800 surface points per view (60 %% foreground), 512 lights, "
@@ -1212,6 +1256,7 @@ def nerf_fp32_class_leg(args, ops, dev, rank, world, barrier, max_over_ranks):
     elapsed, rgb = timed(lambda k: nerf_render_step(ops, views, blobs, None, 'fp32'), steps, 1, barrier)
     elapsed = max_over_ranks(elapsed)
     assert torch.isfinite(rgb).all()
+    keep_output('fp32_class_rgb', rgb)
     n_local = sh.hi - sh.lo
     tf = sh.n_views * n_local * (N_COARSE + N_COARSE + N_FINE) * FLOP_PER_POINT * steps / elapsed / 1e12
     out = {"workload": "the headline NeRF render with precision = fp32 (bf16 hi / lo operand pairs, 3 MFMAs per product)",
@@ -1437,8 +1482,10 @@ def _free_port():
 
 def self_launch(args, argv):
     """`python bench.py --gpus N` with no torchrun around it (the reference's MirroredStrategy is one process that uses every
-    visible GPU, trainvali.py:263-266): re-execute this script as N ranks, one per GPU, under torch.distributed.run on
-    127.0.0.1; rank 0 prints the line.  Refuses — with a JSON error line and a non-zero exit — when the box has fewer GPUs."""
+    visible GPU, trainvali.py:263-266): run this script as N ranks, one per GPU, under torch.distributed.run on 127.0.0.1
+    and exit with its status; rank 0 prints the line.  Refuses — with a JSON error line and a non-zero exit — when the box
+    has fewer GPUs.  The launcher is a CHILD process: counting the GPUs has opened the device in this one, and replacing
+    a process that holds the device with another program (os.exec*) is not safe on the driver."""
     have = torch.cuda.device_count() if torch.cuda.is_available() else 0
     rehearsal = os.environ.get('NFX_BENCH_REHEARSAL') == '1' or os.environ.get('NFX_REHEARSAL') == '1'
     if have < args.gpus and not (rehearsal and have >= 1):
@@ -1449,7 +1496,8 @@ def self_launch(args, argv):
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(args.gpus),
            '--master-addr', '127.0.0.1', '--master-port', str(_free_port()), os.path.abspath(__file__)] + list(argv)
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    import subprocess
+    raise SystemExit(subprocess.call(cmd))
 
 
 # ------------------------------------------------------------------------------------------------ main
@@ -1474,13 +1522,19 @@ def main(argv=None):
                     help="train leg: time the precision = fp32 step in every matrix mode (default: the model's default mode only)")
     ap.add_argument('--force-group', action='store_true',
                     help="one rank: initialise the nccl (RCCL) process group anyway, so that the training legs' all-reduce runs on RCCL")
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help="after the line, write what each timed leg returned in its last timed step (training legs: the loss of "
+                         "every timed step) as DIR/<name>.npy: rank 0's rays, the headline frame whole, other outputs a fixed "
+                         "sample of %d rows; <= 64 MB in all" % DUMP_ROWS)
     argv = sys.argv[1:] if argv is None else argv
     args = ap.parse_args(argv)
-    global MEASURE_TRAFFIC
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    global MEASURE_TRAFFIC, DUMP
     MEASURE_TRAFFIC = args.measure_traffic
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
-        self_launch(args, argv)          # does not return
+        self_launch(args, argv)          # does not return: exits with the ranks' status
     rank = int(os.environ.get('RANK', 0))
     local_rank = int(os.environ.get('LOCAL_RANK', 0))
     world = int(os.environ.get('WORLD_SIZE', 1))
@@ -1493,6 +1547,7 @@ def main(argv=None):
     rehearsal = os.environ.get('NFX_BENCH_REHEARSAL') == '1' or os.environ.get('NFX_REHEARSAL') == '1'
     if rehearsal:
         local_rank = 0
+    DUMP = args.dump_outputs is not None and rank == 0
     torch.cuda.set_device(local_rank)
     dev = torch.device('cuda', local_rank)
     import torch.distributed as dist
@@ -1500,7 +1555,16 @@ def main(argv=None):
     nfx_dist.init_from_env(backend='gloo' if rehearsal else 'nccl', device=None if rehearsal else dev,
                            force=args.force_group)
     from nerfactor_amd import build
-    build.build()
+    try:
+        build.build()
+    except PermissionError:
+        # a tree this user may only read, built by its owner, whose build step opens its lock file before it checks staleness
+        # (build.py before its read-only check; the current one returns early when up to date and raises RuntimeError
+        # when it is not): measure the library built there
+        if not os.path.exists(build.LIB):
+            raise
+        print("bench.py: %s is not writable by this user; measuring the library built there: %s" % (build.OBJDIR, build.LIB),
+              file=sys.stderr, flush=True)
     from nerfactor_amd import ops
 
     def barrier():
@@ -1540,6 +1604,8 @@ def main(argv=None):
     if rank == 0:
         backend = dist.get_backend() if dist.is_initialized() else "none (single process)"
         emit(assemble(args.steps, args.warmup, args.scaling, args.precision, world, backend, rehearsal, legs))
+        if DUMP:
+            dump_outputs(args.dump_outputs)
     if dist.is_initialized():
         dist.destroy_process_group()
 

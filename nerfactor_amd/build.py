@@ -59,7 +59,8 @@ def _headers_mtime():
     return max(os.path.getmtime(h) for h in hs)
 
 
-def _compile(src, force, verbose):
+def _job(src, force):
+    """(source, object, hipcc command line, stale) of one source.  Reads the tree, writes nothing."""
     obj = os.path.join(OBJDIR, src + '.o')
     spath = os.path.join(CSRC, src)
     newest = max(os.path.getmtime(spath), _headers_mtime())
@@ -69,14 +70,19 @@ def _compile(src, force, verbose):
     cmd = [HIPCC] + FLAGS + PER_FILE_FLAGS.get(src, []) + ['-x', 'hip', '-c', spath, '-o', obj]
     stamp = obj + '.cmd'     # the command line is part of the staleness check (per-file flags, NFX_EXTRA_DEFS)
     same_cmd = os.path.exists(stamp) and open(stamp).read() == ' '.join(cmd)
-    if not force and same_cmd and os.path.exists(obj) and os.path.getmtime(obj) >= newest:
+    return src, obj, cmd, force or not (same_cmd and os.path.exists(obj) and os.path.getmtime(obj) >= newest)
+
+
+def _compile(job, verbose):
+    src, obj, cmd, stale = job
+    if not stale:
         return obj, False
     if verbose:
         print(' '.join(cmd), flush=True)
     res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if res.returncode != 0:
         raise RuntimeError('hipcc failed on %s:\n%s' % (src, res.stdout))
-    with open(stamp, 'w') as h:
+    with open(obj + '.cmd', 'w') as h:
         h.write(' '.join(cmd))
     return obj, True
 
@@ -87,14 +93,24 @@ def build(force=False, verbose=False, out=None):
     if out:
         LIB = os.path.abspath(out)
         OBJDIR = os.path.join(ROOT, 'build', 'obj_' + os.path.splitext(os.path.basename(out))[0])
-    os.makedirs(OBJDIR, exist_ok=True)
+    srcs = _sources()
+    # up to date: return before anything is created or opened for writing, so that a tree built by its owner can be used
+    # (tests, bench.py) by a user who may only read it
+    if not force and os.path.exists(LIB) and not any(_job(s, False)[3] for s in srcs):
+        return LIB
+    try:
+        os.makedirs(OBJDIR, exist_ok=True)
+        lock = open(os.path.join(OBJDIR, '.lock'), 'w')
+    except PermissionError as e:
+        raise RuntimeError("%s is missing or out of date and this user cannot write %s: run the build as the tree's owner"
+                           % (LIB, OBJDIR)) from e
     # one builder at a time: the N ranks of a multi-GPU launch all call build(); the first compiles, the others wait
     # on the lock and then find everything up to date
-    with open(os.path.join(OBJDIR, '.lock'), 'w') as lock:
+    with lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
-        srcs = _sources()
+        jobs = [_job(s, force) for s in srcs]
         with ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
-            results = list(ex.map(lambda s: _compile(s, force, verbose), srcs))
+            results = list(ex.map(lambda j: _compile(j, verbose), jobs))
         objs = [o for o, _ in results]
         rebuilt = any(r for _, r in results)
         if rebuilt or not os.path.exists(LIB):

@@ -214,3 +214,40 @@ def test_more_gpus_than_the_box_has_is_a_json_error_line():
     assert len(lines) == 1
     err = json.loads(lines[0], parse_constant=_reject)
     assert 'error' in err and err['n_gpus'] == 8 and err['value'] is None
+
+
+def test_dump_outputs_keeps_the_last_step_in_float_with_a_fixed_sample(monkeypatch, tmp_path):
+    """--dump-outputs: float32 (float64 kept), the headline frame whole, larger outputs of the other legs as the same
+    seeded rows in every run, a dict as one file per key, and never more than the byte budget."""
+    import torch
+    monkeypatch.setattr(bench, 'DUMP', True)
+    monkeypatch.setattr(bench, 'OUTPUTS', {})
+    n = bench.DUMP_ROWS * 3 + 7
+    rgb = torch.arange(n * 3, dtype=torch.float32).reshape(n, 3)
+    bench.keep_output('nerf_rgb', rgb, all_rows=True)
+    bench.keep_output('leg', {'lvis': rgb.to(torch.bfloat16), 'depth': rgb[:, 0].double(), 'small': rgb[:5]})
+    bench.keep_output('train_x_losses', np.array([3., 2., 1.], np.float32))
+    out = dict(bench.OUTPUTS)
+    assert out['nerf_rgb'].dtype == np.float32 and np.array_equal(out['nerf_rgb'], rgb.numpy())
+    assert out['leg_lvis'].dtype == np.float32 and out['leg_lvis'].shape == (bench.DUMP_ROWS, 3)
+    assert out['leg_depth'].dtype == np.float64 and out['leg_depth'].shape == (bench.DUMP_ROWS,)
+    rows = out['leg_depth'] / 3                                                  # sorted, distinct, inside the array
+    assert np.all(np.diff(rows) > 0) and rows.max() < n
+    assert np.array_equal(out['leg_small'], rgb[:5].numpy())
+    monkeypatch.setattr(bench, 'OUTPUTS', {})
+    bench.keep_output('leg', {'lvis': rgb})
+    assert np.array_equal(bench.OUTPUTS['leg_lvis'][:, 0], out['leg_depth'])  # the same rows again
+    names = bench.dump_outputs(str(tmp_path / 'd'), out)
+    assert names == sorted(out) and all(np.array_equal(np.load(tmp_path / 'd' / (k + '.npy')), out[k]) for k in out)
+    with pytest.raises(RuntimeError, match='budget'):
+        bench.dump_outputs(str(tmp_path / 'big'), {'x': np.zeros(bench.DUMP_MAX_BYTES // 4 + 1, np.float32)})
+    monkeypatch.setattr(bench, 'DUMP', False)
+    monkeypatch.setattr(bench, 'OUTPUTS', {})
+    bench.keep_output('nerf_rgb', rgb)
+    assert bench.OUTPUTS == {}
+
+
+def test_steps_below_one_is_a_usage_error():
+    res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'],
+                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert res.returncode == 2 and '--steps must be >= 1' in res.stderr
