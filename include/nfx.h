@@ -155,6 +155,17 @@ NFX_API int nfx_composite_fwd(const float *dev_rgbs, const float *dev_z, const f
                       float *dev_rgb, float *dev_occu, float *dev_depth, float *dev_disp,
                       float *dev_weights, void *stream);
 
+/* The surface of a view's fine pass in one launch (geometry_from_nerf.py process_view, without the [n, S] weights):
+ * compositing as nfx_composite_fwd does (dist |d|, 1e10 behind the last sample, exclusive product of 1 - alpha + 1e-6),
+ * reduced to occu = sum w and depth = sum w z, then occu < occu_thres -> 0, alpha = clamp(occu, 0, 1),
+ * xyz = (rayo + rayd depth) alpha.  quantize_alpha != 0: dev_alpha receives floor(255 alpha + 0.5) / 255 (alpha.png read
+ * back), xyz keeps the unquantised alpha (xyz.npy).  dev_sigma [n_rays, S] (negative values count as 0), dev_z
+ * [n_rays, S], dev_rayo / dev_rayd [n_rays, 3] (rayd unit length); outputs alpha [n], xyz [n, 3], depth [n] (the raw
+ * expected depth), dev_occu [n] (the raw occupancy) or NULL.                                                    */
+NFX_API int nfx_nerf_surface_fwd(const float *dev_sigma, const float *dev_z, const float *dev_rayo, const float *dev_rayd,
+                         int64_t n_rays, int n_samples, float occu_thres, int quantize_alpha, float *dev_alpha,
+                         float *dev_xyz, float *dev_depth, float *dev_occu, void *stream);
+
 /* Hierarchical re-sampling, Model.gen_z_fine + inv_transform_sample
  * (nerf.py:138-147; util/math.py:71-94): pdf over weights[:,1:-1], cdf,
  * searchsorted(side='right'), lerp, then sort(concat(z_coarse, z_fine)).

@@ -49,6 +49,7 @@ SIGNATURES = {
     'nfx_nerf_mlp_fwd': (_i, [_p, _p, _p, _i64, _i, _p, _i, _p, _p]),
     'nfx_composite_fwd': (_i, [_p, _p, _p, _p, _i64, _i, _i, _p, _p, _p, _p, _p, _p]),
     'nfx_sample_fine': (_i, [_p, _p, _i64, _i, _i, _p, _p, _p]),
+    'nfx_nerf_surface_fwd': (_i, [_p, _p, _p, _p, _i64, _i, _f, _i, _p, _p, _p, _p, _p]),
     'nfx_mlp128_xyz_fwd': (_i, [_p, _i64, _f, _p, _i, _i, _f, _f, _i, _p, _p]),
     'nfx_lvis_workspace_bytes': (_sz, [_i64]),
     'nfx_lvis_fwd': (_i, [_p, _p, _i64, _f, _p, _i, _p, _i, _p, _sz, _p, _p]),

@@ -50,6 +50,8 @@ int nfx_launch_composite(const float*, const float*, const float*, const float*,
                          float*, float*, float*, float*, float*, hipStream_t);
 int nfx_launch_sample_fine(const float*, const float*, long long, int, int, const float*, float*,
                            hipStream_t);
+int nfx_launch_surface(const float*, const float*, const float*, const float*, long long, int, float, int, float*, float*,
+                       float*, float*, hipStream_t);
 int nfx_launch_selftest_mfma(const float*, const float*, float*, hipStream_t);
 int nfx_launch_selftest_sincos(const float*, long long, int, float*, hipStream_t);
 
@@ -305,6 +307,20 @@ int nfx_composite_fwd(const float* rgbs, const float* z, const float* rayd, cons
     return hip_result(nfx_launch_composite(rgbs, z, rayd, noise, n_rays, n_samples, white_bg, rgb, occu,
                                            depth, disp, weights, (hipStream_t)stream),
                       "composite_fwd");
+}
+
+int nfx_nerf_surface_fwd(const float* sigma, const float* z, const float* rayo, const float* rayd, int64_t n_rays,
+                         int n_samples, float occu_thres, int quantize_alpha, float* alpha, float* xyz, float* depth,
+                         float* occu, void* stream) {
+    REQUIRE(n_rays >= 0 && n_samples >= 1, "nfx_nerf_surface_fwd: bad shape (%lld rays, %d samples)", (long long)n_rays,
+            n_samples);
+    REQUIRE(occu_thres == occu_thres, "nfx_nerf_surface_fwd: occu_thres is NaN");
+    if (n_rays == 0) return NFX_OK;
+    REQUIRE(sigma && z && rayo && rayd, "nfx_nerf_surface_fwd: null input");
+    REQUIRE(alpha && xyz && depth, "nfx_nerf_surface_fwd: null output (only occu may be NULL)");
+    return hip_result(nfx_launch_surface(sigma, z, rayo, rayd, n_rays, n_samples, occu_thres, quantize_alpha ? 1 : 0, alpha,
+                                         xyz, depth, occu, (hipStream_t)stream),
+                      "nerf_surface_fwd");
 }
 
 int nfx_sample_fine(const float* z, const float* weights, int64_t n_rays, int n_coarse, int n_fine,

@@ -114,6 +114,64 @@ __global__ __launch_bounds__(256) void composite_kernel(
 }
 
 // ---------------------------------------------------------------------------------------
+// surface: the fine pass of the geometry march up to what datasets/nerf_shape.py reads of a test view (alpha, xyz).
+// composite_kernel's scan on the densities alone (sigma[n, S], no rgb), reduced to occupancy and expected depth in
+// registers — the [n, S] weights are never stored — then process_view's epilogue (geometry_from_nerf.py):
+//   occu < occu_thres -> 0;  alpha = clamp(occu, 0, 1);  xyz = (o + d depth) alpha + 0  (_alpha_blend, bg = None);
+//   quantize: alpha_out = floor(255 alpha + 0.5) / 255, what alpha.png read back by load_rgba gives (xyz keeps the
+//   unquantised alpha, as xyz.npy does).  block = 256 threads = 4 rays (one wave each); S any >= 1.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void surface_kernel(
+    const float* __restrict__ sigma, const float* __restrict__ z, const float* __restrict__ rayo,
+    const float* __restrict__ rayd, long long n_rays, int S, float occu_thres, int quantize,
+    float* __restrict__ alpha_out, float* __restrict__ xyz_out, float* __restrict__ depth_out,
+    float* __restrict__ occu_out) {
+    const int lane = threadIdx.x & 63;
+    const long long ray = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;  // wave-uniform
+    const float dx = rayd[3 * ray], dy = rayd[3 * ray + 1], dz = rayd[3 * ray + 2];
+    const float dnorm = sqrtf(dx * dx + dy * dy + dz * dz);
+    const long long base = ray * S;
+    float carry = 1.0f;
+    float s_w = 0.f, s_d = 0.f;
+    for (int s0 = 0; s0 < S; s0 += 64) {
+        const int s = s0 + lane;
+        const bool valid = s < S;
+        const int sc = valid ? s : S - 1;
+        const float zc = z[base + sc];
+        const float zn = (sc < S - 1) ? z[base + sc + 1] : 0.f;
+        float dist = (sc < S - 1) ? (zn - zc) : 1e10f;
+        dist = dist * dnorm;
+        const float alpha = 1.0f - expf(-fmaxf(sigma[base + sc], 0.0f) * dist);
+        const float t = valid ? (1.0f - alpha + 1e-6f) : 1.0f;
+        float incl = t;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const float up = __shfl_up(incl, o, 64);
+            if (lane >= o) incl *= up;
+        }
+        float excl = __shfl_up(incl, 1, 64);
+        if (lane == 0) excl = 1.0f;
+        const float w = valid ? alpha * (carry * excl) : 0.0f;
+        carry = carry * __shfl(incl, 63, 64);
+        s_w += w;
+        s_d += w * zc;
+    }
+    s_w = wave_sum(s_w);
+    s_d = wave_sum(s_d);
+    if (lane == 0) {
+        const float occu = s_w < occu_thres ? 0.0f : s_w;
+        const float a = fminf(fmaxf(occu, 0.0f), 1.0f);
+        xyz_out[3 * ray] = (rayo[3 * ray] + dx * s_d) * a + 0.0f;
+        xyz_out[3 * ray + 1] = (rayo[3 * ray + 1] + dy * s_d) * a + 0.0f;
+        xyz_out[3 * ray + 2] = (rayo[3 * ray + 2] + dz * s_d) * a + 0.0f;
+        alpha_out[ray] = quantize ? floorf(a * 255.0f + 0.5f) / 255.0f : a;
+        depth_out[ray] = s_d;
+        if (occu_out) occu_out[ray] = s_w;
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // refine_select: which COARSE samples decide where the inverse-CDF sampler puts the fine samples (round 6).  One wave
 // per ray, the same scan as composite_kernel (alpha_i, exclusive transmittance T_i).  A sample is listed when it is
 // VISIBLE (T_i > t_min) and either NOT SATURATED (a_lo < alpha_i < a_hi) — a density error there moves the weights of the
@@ -454,6 +512,13 @@ int nfx_launch_composite(const float* rgbs, const float* z, const float* rayd, c
     hipLaunchKernelGGL(nfx::composite_kernel, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, st,
                        (const float4*)rgbs, z, rayd, noise, n_rays, S, white_bg ? 1.0f : 0.0f, rgb,
                        occu, depth, disp, w);
+    return (int)hipGetLastError();
+}
+int nfx_launch_surface(const float* sigma, const float* z, const float* rayo, const float* rayd, long long n_rays, int S,
+                       float occu_thres, int quantize, float* alpha, float* xyz, float* depth, float* occu, hipStream_t st) {
+    if (n_rays <= 0) return 0;
+    hipLaunchKernelGGL(nfx::surface_kernel, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, st, sigma, z, rayo, rayd,
+                       n_rays, S, occu_thres, quantize, alpha, xyz, depth, occu);
     return (int)hipGetLastError();
 }
 int nfx_launch_refine_select(const float* rgbs, const float* z, const float* rayd, long long n_rays, int S, float t_min,

@@ -167,6 +167,11 @@ class Model(ShapeModel):
                                  brdf_z_override, xyz_noise)
         xyz_jitter_std = self.config.getfloat('DEFAULT', 'xyz_jitter_std')
         id_, hw, rayo, _, rgb, alpha, xyz, normal, lvis = batch
+        # a batch marched from camera rays (nerfactor/surface.py, render_from_nerf.py) has no normal / lvis
+        surface_only = normal is None and lvis is None
+        if surface_only and self.shape_mode == 'nerf':
+            raise ValueError("shape_mode = nerf reads the normals and light visibility of the batch: render from the "
+                             "surface buffers geometry_from_nerf writes (datasets/nerf_shape.py)")
         n_all = alpha.shape[0]
         # training batches are foreground rays only (datasets/nerf_shape.py:102-107) and say so: no compaction, and
         # above all no torch.nonzero, whose row count the host can only read after the whole previous step has drained
@@ -177,7 +182,7 @@ class Model(ShapeModel):
             all_fg = idx.numel() == n_all
         rgb_all, normal_all, lvis_all = rgb, normal, lvis
         if not all_fg:                  # no gather here and no zero-filled scatter at the end (~40 tiny launches)
-            rayo, rgb, xyz, normal = (t[idx].contiguous() for t in (rayo, rgb, xyz, normal))
+            rayo, rgb, xyz, normal = (None if t is None else t[idx].contiguous() for t in (rayo, rgb, xyz, normal))
             # the [n, 512] ground-truth visibility is only gathered where it is an INPUT (shape_mode = nerf); as an
             # output (gt['lvis'] = scatter of the gathered rows) it is one masked copy, not gather + fill + scatter
             lvis = lvis[idx].contiguous() if self.shape_mode == 'nerf' else None
@@ -273,7 +278,10 @@ class Model(ShapeModel):
             pred['rgb_olat'] = full(rgb_olat)
         if rgb_probes is not None:
             pred['rgb_probes'] = full(rgb_probes)
-        if all_fg:
+        if surface_only:   # no ground-truth normal / visibility: gt simply lacks them (no gt_normal / gt_lvis image)
+            fg = alpha[:, :1] > 0
+            gt = {'rgb': rgb if all_fg else torch.where(fg, rgb_all, torch.zeros_like(rgb_all)), 'alpha': alpha}
+        elif all_fg:
             gt = {'rgb': rgb, 'normal': normal, 'lvis': lvis, 'alpha': alpha}
         else:   # tf.scatter_nd of the foreground rows = the inputs with the background rows zeroed
             fg = alpha[:, :1] > 0

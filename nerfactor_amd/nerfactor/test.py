@@ -69,18 +69,11 @@ def get_albedo_override(name, xyz, axis_i, axis_min, axis_max):
     raise NotImplementedError("Target albedo: %s" % name)
 
 
-def main(argv=None):
-    args = parse_args(argv)
-    if not torch.cuda.is_available():
-        raise RuntimeError("test needs an MI355X: libnfx has no CPU path")
-    device = nfx_dist.local_device()
-    rank, ws = nfx_dist.init_from_env(device=device)
-    _, outroot, dataset, datapipe, model = setup(args.ckpt, args.debug, device)
+def edit_setup(args, model, outroot):
+    """(output root with the edit's suffix, albedo_scales, brdf_z_override) of the editing flags."""
     for suffix in (args.tgt_albedo, args.tgt_brdf):
         if suffix:
             outroot = outroot.rstrip('/') + '_%s' % suffix
-    n_views = dataset.get_n_views()
-
     albedo_scales = None
     if not args.tgt_albedo and args.color_correct_albedo:
         albedo_scales = compute_rgb_scales(args.ckpt)
@@ -88,17 +81,37 @@ def main(argv=None):
     if args.tgt_brdf:
         brdf = model.brdf_model
         brdf_z_override = brdf.latent_code.z[brdf.brdf_names.index(args.tgt_brdf), :].detach()
+    return outroot, albedo_scales, brdf_z_override
+
+
+def render_test_view(model, batch, outdir, args, relight_olat, albedo_scales=None, brdf_z_override=None, sharded=False):
+    """One test view: probes relit, OLAT if `relight_olat`, the editing flags of `args`; rank 0 writes the images.
+    `batch` is the whole view (each rank renders its contiguous ray range of it) or, with `sharded`, already this rank's
+    range (render_from_nerf.py marches only its own rays)."""
+    albedo_override = None
+    if args.tgt_albedo:
+        albedo_override = get_albedo_override(args.tgt_albedo, batch[6], args.sv_axis_i, args.sv_axis_min, args.sv_axis_max)
+        if not sharded:   # evaluated on the whole view, then cut to this rank's rays like the batch itself
+            albedo_override = shard.shard_rows(albedo_override, batch[6].shape[0])
+    return shard.render_view(
+        model, batch, outdir, mode='test', sharded=sharded, relight_olat=relight_olat, relight_probes=True,
+        albedo_scales=albedo_scales, albedo_override=albedo_override, brdf_z_override=brdf_z_override)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    if not torch.cuda.is_available():
+        raise RuntimeError("test needs an MI355X: libnfx has no CPU path")
+    device = nfx_dist.local_device()
+    rank, ws = nfx_dist.init_from_env(device=device)
+    _, outroot, dataset, datapipe, model = setup(args.ckpt, args.debug, device)
+    outroot, albedo_scales, brdf_z_override = edit_setup(args, model, outroot)
+    n_views = dataset.get_n_views()
 
     for batch_i, batch in enumerate(datapipe):
-        relight_olat = batch_i == n_views - 1
-        albedo_override = None
-        if args.tgt_albedo:   # evaluated on the whole view, then cut to this rank's rays like the batch itself
-            albedo_override = shard.shard_rows(get_albedo_override(
-                args.tgt_albedo, batch[6], args.sv_axis_i, args.sv_axis_min, args.sv_axis_max), batch[6].shape[0])
-        shard.render_view(
-            model, batch, join(outroot, 'batch{i:09d}'.format(i=batch_i)), mode='test', relight_olat=relight_olat,
-            relight_probes=True, albedo_scales=albedo_scales, albedo_override=albedo_override,
-            brdf_z_override=brdf_z_override)
+        render_test_view(model, batch, join(outroot, 'batch{i:09d}'.format(i=batch_i)), args,
+                         relight_olat=batch_i == n_views - 1, albedo_scales=albedo_scales,
+                         brdf_z_override=brdf_z_override)
         if args.debug:
             break
     nfx_dist.barrier()

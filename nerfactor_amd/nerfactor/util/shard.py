@@ -45,9 +45,10 @@ def gather_rows(rows):
     return out if rank == 0 else None
 
 
-def render_view(model, batch, outdir, mode='test', **call_kwargs):
-    """model(batch shard, mode, **call_kwargs) on this rank's rays of one view -> PNGs written by rank 0."""
-    _, _, _, to_vis = model(shard_batch(batch), mode=mode, **call_kwargs)
+def render_view(model, batch, outdir, mode='test', sharded=False, **call_kwargs):
+    """model(batch shard, mode, **call_kwargs) on this rank's rays of one view -> PNGs written by rank 0.  `sharded`: the
+    batch holds this rank's rays only already."""
+    _, _, _, to_vis = model(batch if sharded else shard_batch(batch), mode=mode, **call_kwargs)
     rows = gather_rows(model.vis_rows(to_vis))
     if rows is not None:
         model.write_vis(rows, outdir)

@@ -322,6 +322,26 @@ def composite_fwd(rgbs, z, rayd, white_bg=True, noise=None, want_weights=True):
     return rgb, occu, depth, disp, w
 
 
+def nerf_surface(sigma, z, rayo, rayd, occu_thres=0., quantize_alpha=True, want_occu=False):
+    """(alpha[N], xyz[N,3], depth[N], occu[N] or None) of the fine densities sigma[N,S] at depths z[N,S] along unit
+    rays: compositing, occupancy / expected depth and geometry_from_nerf.process_view's epilogue in one launch
+    (nfx_nerf_surface_fwd)."""
+    sigma = _dev(sigma, 'sigma', (None, None))
+    n, s = sigma.shape
+    z = _dev(z, 'z', (n, s))
+    rayo = _dev(rayo, 'rayo', (n, 3))
+    rayd = _dev(rayd, 'rayd', (n, 3))
+    dev = sigma.device
+    alpha = torch.empty((n,), dtype=torch.float32, device=dev)
+    xyz = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    depth = torch.empty_like(alpha)
+    occu = torch.empty_like(alpha) if want_occu else None
+    check(lib.nfx_nerf_surface_fwd(_ptr(sigma), _ptr(z), _ptr(rayo), _ptr(rayd), n, s, float(occu_thres),
+                                   int(bool(quantize_alpha)), _ptr(alpha), _ptr(xyz), _ptr(depth), _ptr(occu),
+                                   _stream()), 'nfx_nerf_surface_fwd')
+    return alpha, xyz, depth, occu
+
+
 def sample_fine(z, weights, n_fine, u=None):
     z = _dev(z, 'z', (None, None))
     n, nc = z.shape
