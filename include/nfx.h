@@ -503,6 +503,36 @@ NFX_API int nfx_nerf_sigma_refine(const float *dev_rayo, const float *dev_rayd, 
                           int n_samples, const void *dev_geom_blob_fp32, const int *dev_list, const int *dev_count,
                           float *dev_rgbs, void *stream);
 
+/* Occupancy grid of the density marches (csrc/occgrid.hip): R^3 cells over a box
+ * (x_min, x_max, y_min, y_max, z_min, z_max; host floats, finite, min < max), one bit per cell — cell (i, j, k), i along x,
+ * is bit c & 31 of word c >> 5 of dev_bits[ceil(R^3 / 32)], c = (i R + j) R + k; a point p with box_lo <= p <= box_hi lies in
+ * cell min(floor((p - lo) / (hi - lo) * R), R - 1) per axis.  1 <= R <= NFX_OCCGRID_MAX_RES.
+ *   nfx_occgrid_select       lists the samples of sigma[n_rays, S] the density kernel has to evaluate: the point
+ *                            rayo + rayd z (fp32 multiply, then add) outside the box or in a set cell; never a point
+ *                            outside the optional `bbox` (host, 6 floats or NULL: p < min or p > max on an axis).  Writes
+ *                            0.0f to dev_sigma at every unlisted sample.  Three launches, no host sync.  `workspace`:
+ *                            nfx_occgrid_workspace_bytes, 16-byte aligned, int32 words [count, 3 pad][ceil(n / 1024)
+ *                            block counts, padded to 4][the list: ascending flat indices ray * S + s], n = n_rays S < 2^31;
+ *   nfx_nerf_sigma_fwd_list  sigma[i] for the flat indices i = dev_list[0 .. *dev_count) (the count is read on the device),
+ *                            bit-identical to nfx_nerf_sigma_fwd at those samples; leaves every other sample alone;
+ *   nfx_occgrid_bake         the grid from the raw densities of a lattice of M = R P points per axis (point (a, b, c) at
+ *                            lo + (idx + 0.5) / M (hi - lo) per axis, stored at dev_probe_sigma[(a M + b) M + c]: cell
+ *                            (i, j, k) holds P^3 of them): a cell is occupied when a probe has sigma_raw > -margin (or is
+ *                            NaN); its bit is set when an occupied cell lies within `dilate` cells on every axis.
+ *                            1 <= P <= 16, (R P)^3 <= NFX_OCCGRID_MAX_PROBES, 0 <= dilate <= 16; `dev_workspace`: as
+ *                            many words as dev_bits (the separable dilation's other buffer).                           */
+#define NFX_OCCGRID_MAX_RES 1024
+#define NFX_OCCGRID_MAX_PROBES (1ll << 30)
+NFX_API int nfx_nerf_sigma_fwd_list(const float *dev_rayo, const float *dev_rayd, const float *dev_z, int64_t n_rays,
+                            int n_samples, const void *dev_geom_blob, int prec, const int *dev_list,
+                            const int *dev_count, float *dev_sigma, void *stream);
+NFX_API size_t nfx_occgrid_workspace_bytes(int64_t n_rays, int n_samples);
+NFX_API int nfx_occgrid_select(const float *dev_rayo, const float *dev_rayd, const float *dev_z, int64_t n_rays,
+                       int n_samples, const uint32_t *dev_bits, int res, const float *box, const float *bbox,
+                       float *dev_sigma, void *dev_workspace, size_t workspace_bytes, void *stream);
+NFX_API int nfx_occgrid_bake(const float *dev_probe_sigma, int res, int probes, float margin, int dilate,
+                     uint32_t *dev_bits, uint32_t *dev_workspace, void *stream);
+
 /* ------------------------------------------------------------------------ */
 /* Diagnostics.                                                              */
 /* ------------------------------------------------------------------------ */

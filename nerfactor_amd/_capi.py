@@ -97,6 +97,10 @@ SIGNATURES = {
     'nfx_shade_olat_fwd_rows': (_i, [_p, _p, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _f, _f, _i64, _i, _i, _p, _p, _p, _p]),
     'nfx_nerf_refine_select': (_i, [_p, _p, _p, _i64, _i, _f, _f, _f, _f, _i, _p, _p, _p]),
     'nfx_nerf_sigma_refine': (_i, [_p, _p, _p, _i64, _i, _p, _p, _p, _p, _p]),
+    'nfx_nerf_sigma_fwd_list': (_i, [_p, _p, _p, _i64, _i, _p, _i, _p, _p, _p, _p]),
+    'nfx_occgrid_workspace_bytes': (_sz, [_i64, _i]),
+    'nfx_occgrid_select': (_i, [_p, _p, _p, _i64, _i, _p, _i, _p, _p, _p, _p, _sz, _p]),
+    'nfx_occgrid_bake': (_i, [_p, _i, _i, _f, _i, _p, _p, _p]),
     'nfx_nerf_geom_packed_bytes': (_sz, [_i]),
     'nfx_nerf_pack_geom_weights': (_i, [_pp, _pp, _i, _p, _sz]),
     'nfx_nerf_sigma_grad': (_i, [_p, _p, _p, _i64, _i, _p, _i, _p, _p]),

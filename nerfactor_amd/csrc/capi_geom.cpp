@@ -1,6 +1,7 @@
 // capi_geom.cpp — C-ABI entry points of the geometry-extraction kernels (include/nfx.h): density only, and density
 // with its spatial gradient (geometry_from_nerf.py:249-350).
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <string.h>
 
 #include <vector>
@@ -39,6 +40,14 @@ int nfx_launch_nerf_sigma_x3(const float*, const float*, const float*, long long
                              hipStream_t);   // nerf_geom_x3.hip
 int nfx_launch_nerf_sigma_grad_x3(const float*, const float*, const float*, long long, int, const void*, float*, int,
                                   hipStream_t);
+int nfx_launch_nerf_sigma_v6_list(const float*, const float*, const float*, long long, int, const void*, float*, const int*,
+                                  const int*, int, hipStream_t);   // nerf_sigma_v6.hip
+int nfx_launch_nerf_sigma_x3_list_flat(const float*, const float*, const float*, long long, int, const void*, float*,
+                                       const int*, const int*, int, hipStream_t);
+size_t nfx_occgrid_list_bytes(long long n_pts);   // occgrid.hip
+int nfx_launch_occgrid_select(const float*, const float*, const float*, long long, int, const uint32_t*, int, const float*,
+                              const float*, float*, void*, hipStream_t);
+int nfx_launch_occgrid_bake(const float*, int, int, float, int, uint32_t*, uint32_t*, hipStream_t);
 
 size_t nfx_nerf_geom_packed_bytes(int prec) {
     using namespace nfx::nerf;
@@ -251,5 +260,68 @@ int nfx_nerf_sigma_grad_rows(const float* rayo, const float* rayd, const float* 
                               : nfx_launch_nerf_sigma_grad_list(rayo, rayd, z, n_pts, n_samples, geom_blob, normal_sigma,
                                                                 list, count, blocks, st),
                           "nerf_sigma_grad_rows(gradient)");
+}
+
+// ---------------------------------------------------------------- occupancy grid (occgrid.hip)
+int nfx_nerf_sigma_fwd_list(const float* rayo, const float* rayd, const float* z, int64_t n_rays, int n_samples,
+                            const void* blob, int prec, const int* list, const int* count, float* sigma, void* stream) {
+    REQUIRE(n_rays >= 0 && n_samples >= 1, "nfx_nerf_sigma_fwd_list: bad shape");
+    REQUIRE(prec == NFX_PREC_BF16 || prec == NFX_PREC_FP32, "nfx_nerf_sigma_fwd_list: bad prec %d", prec);
+    if (n_rays == 0) return NFX_OK;
+    const long long n_pts = (long long)n_rays * n_samples;
+    REQUIRE(n_pts < (1ll << 31), "nfx_nerf_sigma_fwd_list: %lld samples do not fit int32 indices", n_pts);
+    REQUIRE(rayo && rayd && z && blob && list && count && sigma, "nfx_nerf_sigma_fwd_list: null pointer");
+    if (!ALIGNED(blob, 16)) return nfx_fail(NFX_EALIGN, "nfx_nerf_sigma_fwd_list: blob must be 16-byte aligned");
+    const int blocks = nfx_option_int("nerf_blocks", 256);
+    hipStream_t st = (hipStream_t)stream;
+    return nfx_hip_result(prec == NFX_PREC_FP32
+                              ? nfx_launch_nerf_sigma_x3_list_flat(rayo, rayd, z, n_pts, n_samples, blob, sigma, list, count,
+                                                                   blocks, st)
+                              : nfx_launch_nerf_sigma_v6_list(rayo, rayd, z, n_pts, n_samples, blob, sigma, list, count,
+                                                              blocks, st),
+                          "nerf_sigma_fwd_list");
+}
+
+size_t nfx_occgrid_workspace_bytes(int64_t n_rays, int n_samples) {
+    if (n_rays <= 0 || n_samples <= 0) return 0;
+    return nfx_occgrid_list_bytes((long long)n_rays * n_samples);
+}
+
+static bool valid_box(const float* b) {
+    for (int k = 0; k < 3; ++k)
+        if (!(b[2 * k] < b[2 * k + 1]) || !isfinite(b[2 * k]) || !isfinite(b[2 * k + 1])) return false;
+    return true;
+}
+
+int nfx_occgrid_select(const float* rayo, const float* rayd, const float* z, int64_t n_rays, int n_samples,
+                       const uint32_t* bits, int res, const float* box, const float* bbox, float* sigma, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    REQUIRE(n_rays >= 0 && n_samples >= 1, "nfx_occgrid_select: bad shape");
+    REQUIRE(res >= 1 && res <= NFX_OCCGRID_MAX_RES, "nfx_occgrid_select: res = %d (1 .. %d)", res, NFX_OCCGRID_MAX_RES);
+    REQUIRE(box && valid_box(box), "nfx_occgrid_select: box must be finite with min < max on every axis");
+    if (n_rays == 0) return NFX_OK;
+    const long long n_pts = (long long)n_rays * n_samples;
+    REQUIRE(n_pts < (1ll << 31), "nfx_occgrid_select: %lld samples do not fit int32 indices", n_pts);
+    REQUIRE(rayo && rayd && z && bits && sigma && workspace, "nfx_occgrid_select: null pointer");
+    REQUIRE(workspace_bytes >= nfx_occgrid_workspace_bytes(n_rays, n_samples), "nfx_occgrid_select: workspace too small");
+    if (!ALIGNED(workspace, 16)) return nfx_fail(NFX_EALIGN, "nfx_occgrid_select: workspace must be 16-byte aligned");
+    return nfx_hip_result(nfx_launch_occgrid_select(rayo, rayd, z, n_pts / n_samples, n_samples, bits, res, box, bbox, sigma,
+                                                    workspace, (hipStream_t)stream),
+                          "occgrid_select");
+}
+
+int nfx_occgrid_bake(const float* probe_sigma, int res, int probes, float margin, int dilate, uint32_t* bits,
+                     uint32_t* workspace, void* stream) {
+    REQUIRE(res >= 1 && res <= NFX_OCCGRID_MAX_RES, "nfx_occgrid_bake: res = %d (1 .. %d)", res, NFX_OCCGRID_MAX_RES);
+    REQUIRE(probes >= 1 && probes <= 16, "nfx_occgrid_bake: probes = %d (1 .. 16 per axis)", probes);
+    const long long m = (long long)res * probes;
+    REQUIRE(m * m * m <= NFX_OCCGRID_MAX_PROBES, "nfx_occgrid_bake: (res probes)^3 = %lld probes (at most %lld)", m * m * m,
+            (long long)NFX_OCCGRID_MAX_PROBES);
+    REQUIRE(dilate >= 0 && dilate <= 16, "nfx_occgrid_bake: dilate = %d (0 .. 16)", dilate);
+    REQUIRE(isfinite(margin), "nfx_occgrid_bake: margin must be finite");
+    REQUIRE(probe_sigma && bits && workspace, "nfx_occgrid_bake: null pointer");
+    return nfx_hip_result(nfx_launch_occgrid_bake(probe_sigma, res, probes, margin, dilate, bits, workspace,
+                                                  (hipStream_t)stream),
+                          "occgrid_bake");
 }
 }  // extern "C"

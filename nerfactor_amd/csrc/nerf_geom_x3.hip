@@ -70,12 +70,13 @@ template <bool GRAD>
 __global__ __launch_bounds__(kNW * 64, 1) void nerf_sigma_x3_kernel(
     const float* __restrict__ rayo, const float* __restrict__ rayd, const float* __restrict__ zbuf, long long n_pts,
     int n_samples, const char* __restrict__ blob, float* __restrict__ out, const int* __restrict__ list,
-    const int* __restrict__ count) {
+    const int* __restrict__ count, int list_stride) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using namespace nerf;
     // LIST mode (round 6): the points are the flat sample indices list[0 .. *count) (both in device memory: the number of
-    // selected samples never visits the host).  Density only (the selective coarse refinement of the bf16 render): the
-    // density of point i goes to out[4 i + 3] — the sigma channel of rgbs[N, S, 4]; GRAD (nfx_nerf_sigma_grad_rows: the
+    // selected samples never visits the host).  Density only: the density of point i goes to out[list_stride (i + 1) - 1] —
+    // list_stride = 4: the sigma channel of rgbs[N, S, 4] (the selective coarse refinement of the bf16 render); 1: a flat
+    // [N, S] (nfx_nerf_sigma_fwd_list, the occupancy-grid march); GRAD (nfx_nerf_sigma_grad_rows: the
     // samples with a positive density): (normal, sigma) of point i to row i of out[n][4].  A workgroup with no tile leaves at once.
     if (list != nullptr) {
         n_pts = *count;
@@ -131,7 +132,7 @@ __global__ __launch_bounds__(kNW * 64, 1) void nerf_sigma_x3_kernel(
         }
         if constexpr (!GRAD) {
             if (valid && h == 0) {
-                if (list != nullptr) out[4 * mm + 3] = sigma;
+                if (list != nullptr) out[list_stride * (mm + 1) - 1] = sigma;
                 else out[row] = sigma;
             }
         } else {
@@ -189,7 +190,7 @@ __global__ __launch_bounds__(kNW * 64, 1) void nerf_sigma_x3_kernel(
 template <bool GRAD>
 static int launch(const float* rayo, const float* rayd, const float* z, long long n_pts, int n_samples,
                   const void* blob, float* out, int max_blocks, hipStream_t st, const int* list = nullptr,
-                  const int* count = nullptr) {
+                  const int* count = nullptr, int list_stride = 4) {
     if (n_pts <= 0) return 0;
     const long long tiles = (n_pts + kRows - 1) / kRows;
     const int grid = (int)(tiles < max_blocks ? tiles : max_blocks);
@@ -197,7 +198,7 @@ static int launch(const float* rayo, const float* rayd, const float* z, long lon
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(k, dim3(grid), dim3(kNW * 64), kLds, st, rayo, rayd, z, n_pts, n_samples, (const char*)blob, out,
-                       list, count);
+                       list, count, list_stride);
     return (int)hipGetLastError();
 }
 
@@ -224,4 +225,10 @@ extern "C" int nfx_launch_nerf_sigma_x3_list(const float* rayo, const float* ray
                                              int n_samples, const void* blob, float* rgbs, const int* list,
                                              const int* count, int max_blocks, hipStream_t st) {
     return nfx::geo3::launch<false>(rayo, rayd, z, n_pts, n_samples, blob, rgbs, max_blocks, st, list, count);
+}
+// ... with each density at out[i] of a flat [N, S] (nfx_nerf_sigma_fwd_list at NFX_PREC_FP32)
+extern "C" int nfx_launch_nerf_sigma_x3_list_flat(const float* rayo, const float* rayd, const float* z, long long n_pts,
+                                                  int n_samples, const void* blob, float* out, const int* list,
+                                                  const int* count, int max_blocks, hipStream_t st) {
+    return nfx::geo3::launch<false>(rayo, rayd, z, n_pts, n_samples, blob, out, max_blocks, st, list, count, 1);
 }

@@ -4,6 +4,7 @@ outputs (nerfactor/geometry_from_nerf.py:30-391):
     [torchrun --nproc-per-node N] python -m nerfactor_amd.nerfactor.geometry_from_nerf \\
         --trained_nerf=<outroot>/<xname> --out_root=<dir> [--imh H] [--scene_bbox x0,x1,y0,y1,z0,z1]
         [--lvis_far 1] [--occu_thres 0] [--light_h 16] [--spp 1] [--debug]
+        [--occupancy_grid R [--grid_margin 10] [--grid_dilate 2] [--grid_probes 4] [--grid_check K]]
 
 For every view of every split writes <out_root>/<view id>/{alpha.png, xyz.npy, xyz.png, normal.npy, normal.png,
 lvis.npy, lvis.png} — what datasets/nerf_shape.py reads.  All marching runs on libnfx:
@@ -14,7 +15,10 @@ lvis.npy, lvis.png} — what datasets/nerf_shape.py reads.  All marching runs on
   * shadow rays: every (surface point, front-lit light) pair is a ray from lvis_near = 0.1 to lvis_far marched with the
     density-only kernel (nfx_nerf_sigma_fwd), lvis = 1 - sum(weights).
 With N ranks the rays of EVERY view are split into N contiguous ranges: each rank marches its rays and
-writes its rows of the .npy files; rank 0 receives uint8 preview rows only."""
+writes its rows of the .npy files; rank 0 receives uint8 preview rows only.
+--occupancy_grid R (opt-in, occupancy.py): the density-only passes (the coarse pass of the camera rays, both passes of the
+shadow rays) evaluate only the samples whose cell of an R^3 grid baked from the NeRF may hold density — the same outputs
+wherever no skipped sample has a density (--grid_check K proves that on the scene)."""
 import argparse
 import glob
 import os
@@ -28,7 +32,7 @@ from PIL import Image
 
 from .. import dist as nfx_dist
 from ..brdf.renderer import gen_light_xyz
-from . import datasets, models
+from . import datasets, models, occupancy
 from .util import config as configutil
 
 
@@ -47,6 +51,7 @@ def parse_args(argv=None):
     ap.add_argument('--spp', type=int, default=1, help="samples per pixel")
     ap.add_argument('--fps', type=int, default=12, help="accepted for compatibility (no video is written)")
     ap.add_argument('--debug', action='store_true')
+    occupancy.add_arguments(ap)
     return ap.parse_args(argv)
 
 
@@ -62,8 +67,9 @@ def latest_checkpoint(trained_nerf):
     return max(found, key=lambda p: int(p.rsplit('-', 1)[1]))
 
 
-def _march(model, rayo, rayd, near, far, n_coarse, n_fine, lin_in_disp, bbox, want_normal, rays_per_call):
-    """Coarse + importance-sampled density march of `rayo + rayd z`, z in [near, far]; returns (occu, depth, normal)."""
+def _march(model, rayo, rayd, near, far, n_coarse, n_fine, lin_in_disp, bbox, want_normal, rays_per_call, grid=None):
+    """Coarse + importance-sampled density march of `rayo + rayd z`, z in [near, far]; returns (occu, depth, normal).
+    `grid` (occupancy.OccupancyGrid): the density-only passes evaluate the samples it lists (not the gradient pass)."""
     n = rayo.shape[0]
     occu = torch.empty(n, device=rayo.device)
     depth = torch.empty_like(occu)
@@ -71,12 +77,12 @@ def _march(model, rayo, rayd, near, far, n_coarse, n_fine, lin_in_disp, bbox, wa
     for lo in range(0, n, rays_per_call):
         o, d = rayo[lo:lo + rays_per_call].contiguous(), rayd[lo:lo + rays_per_call].contiguous()
         z = model.gen_z(near, far, n_coarse, o.shape[0], lin_in_disp=lin_in_disp, perturb=False, device=o.device)
-        w = model.accumulate_sigma(model.eval_sigma(o, d, z, use_fine=False, bbox=bbox), z, d)
+        w = model.accumulate_sigma(model.eval_sigma(o, d, z, use_fine=False, bbox=bbox, grid=grid), z, d)
         z = model.gen_z_fine(z, w, n_fine, perturb=False)
         if want_normal:
             sigma, nrm = model.eval_sigma_normal(o, d, z, bbox=bbox)
         else:
-            sigma, nrm = model.eval_sigma(o, d, z, use_fine=True, bbox=bbox), None
+            sigma, nrm = model.eval_sigma(o, d, z, use_fine=True, bbox=bbox, grid=grid), None
         w = model.accumulate_sigma(sigma, z, d)
         occu[lo:lo + rays_per_call] = w.sum(-1)
         depth[lo:lo + rays_per_call] = (w * z).sum(-1)
@@ -90,17 +96,19 @@ def _sample_counts(config):
             config.getboolean('DEFAULT', 'lin_in_disp'))
 
 
-def compute_depth_and_normal(model, rayo, rayd, config, bbox=None, mlp_chunk=1 << 25):
-    """(occu[N], exp_depth[N], exp_normal[N,3]) — geometry_from_nerf.py:249-319."""
+def compute_depth_and_normal(model, rayo, rayd, config, bbox=None, mlp_chunk=1 << 25, grid=None):
+    """(occu[N], exp_depth[N], exp_normal[N,3]) — geometry_from_nerf.py:249-319.  `grid`: the coarse pass only (the fine
+    pass is the density gradient, which lists the samples with a density itself)."""
     n_coarse, n_fine, lin_in_disp = _sample_counts(config)
     rays = max(1, mlp_chunk // (n_coarse + n_fine))
     return _march(model, rayo, rayd, config.getfloat('DEFAULT', 'near'), config.getfloat('DEFAULT', 'far'), n_coarse,
-                  n_fine, lin_in_disp, bbox, True, rays)
+                  n_fine, lin_in_disp, bbox, True, rays, grid)
 
 
 def compute_light_visibility(model, surf, normal, config, lvis_far=1., light_h=16, bbox=None, lvis_near=.1,
-                             mlp_chunk=1 << 25):
-    """lvis[n_surf, n_lights] = 1 - occupancy along surface -> light, 0 for back-lit pairs (:177-246)."""
+                             mlp_chunk=1 << 25, grid=None):
+    """lvis[n_surf, n_lights] = 1 - occupancy along surface -> light, 0 for back-lit pairs (:177-246).  `grid`: both
+    density passes of the shadow rays."""
     n_coarse, n_fine, lin_in_disp = _sample_counts(config)
     lxyz, _ = gen_light_xyz(light_h, 2 * light_h)
     lxyz = torch.as_tensor(lxyz.reshape(-1, 3).astype(np.float32), device=surf.device)
@@ -116,7 +124,7 @@ def compute_light_visibility(model, surf, normal, config, lvis_far=1., light_h=1
             continue
         o = s[:, None, :].expand(-1, n_lights, -1)[front]
         occu, _, _ = _march(model, o, surf2l[front], lvis_near, lvis_far, n_coarse, n_fine, lin_in_disp, bbox, False,
-                            rays_per_call)
+                            rays_per_call, grid)
         block = lvis[lo:lo + pts_per_call]
         block[front] = 1. - occu
     return lvis
@@ -136,7 +144,7 @@ def _write_png(path, arr):
     Image.fromarray(arr).save(path)
 
 
-def process_view(config, model, batch, args, bbox):
+def process_view(config, model, batch, args, bbox, grid=None):
     sps = int(np.sqrt(args.spp))
     id_, hw, rayo, rayd, _ = batch
     id_ = id_[0]
@@ -157,7 +165,7 @@ def process_view(config, model, batch, args, bbox):
     rayo, rayd = rayo[lo:hi], rayd[lo:hi]
     rayd = torch.nn.functional.normalize(rayd, dim=1, eps=1e-12)
     # ------ camera -> object
-    occu, exp_depth, exp_normal = compute_depth_and_normal(model, rayo, rayd, config, bbox, args.mlp_chunk)
+    occu, exp_depth, exp_normal = compute_depth_and_normal(model, rayo, rayd, config, bbox, args.mlp_chunk, grid=grid)
     occu = torch.where(occu < args.occu_thres, torch.zeros_like(occu), occu)
     alpha = occu.clamp(0., 1.)                                   # average_supersamples is the identity at spp = 1
     surf = rayo + rayd * exp_depth[:, None]
@@ -171,9 +179,10 @@ def process_view(config, model, batch, args, bbox):
     lvis = torch.zeros((hi - lo, n_lights), device=rayo.device)
     if bool(hit.any()):
         lvis_hit = compute_light_visibility(model, surf[hit], exp_normal[hit], config, lvis_far=args.lvis_far,
-                                            light_h=args.light_h, bbox=bbox, mlp_chunk=args.mlp_chunk)
+                                            light_h=args.light_h, bbox=bbox, mlp_chunk=args.mlp_chunk, grid=grid)
         lvis[hit] = lvis_hit.clamp(0., 1.)
     lvis = lvis * alpha[:, None]
+    occupancy.log_view(grid, id_, 'geometry_from_nerf')
     # ------ writers (util/geom.py:27-79): .npy rows by every rank, previews by rank 0
     shapes = {'xyz': (h, w, 3), 'normal': (h, w, 3), 'lvis': (h, w, n_lights)}
     if rank == 0:
@@ -214,6 +223,7 @@ def _global_min_max(t):
 
 def main(argv=None):
     args = parse_args(argv)
+    occupancy.check_arguments(args)
     if not torch.cuda.is_available():
         raise RuntimeError("geometry_from_nerf needs an MI355X: libnfx has no CPU path")
     if int(np.sqrt(args.spp)) ** 2 != args.spp:
@@ -235,6 +245,7 @@ def main(argv=None):
     model = Model(config).to(device)
     configutil.restore_model(model, ckpt)
     model.to(device)
+    grid = occupancy.from_arguments(args, model, bbox, config.get('DEFAULT', 'data_root'))
     Dataset = datasets.get_dataset_class(config.get('DEFAULT', 'dataset'))
     done, i = [], 0
     with torch.no_grad():
@@ -244,7 +255,7 @@ def main(argv=None):
             except FileNotFoundError:
                 continue
             for batch in dataset.build_pipeline(no_batch=config.getboolean('DEFAULT', 'no_batch'), no_shuffle=True):
-                done.append(process_view(config, model, batch, args, bbox))   # every rank: its rays of this view
+                done.append(process_view(config, model, batch, args, bbox, grid))   # every rank: its rays of this view
                 i += 1
                 if args.debug:
                     break

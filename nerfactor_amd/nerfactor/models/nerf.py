@@ -375,15 +375,33 @@ class Model(BaseModel):
         hi = pts.new_tensor(bbox[1::2])
         return ((pts >= lo) & (pts <= hi)).all(-1)
 
-    def eval_sigma(self, rayo, rayd, z, use_fine=False, bbox=None):
+    def eval_sigma(self, rayo, rayd, z, use_fine=False, bbox=None, grid=None):
         """relu(sigma)[N,S] at rayo + rayd z (eval_sigma_mlp, geometry_from_nerf.py:322-350); outside the optional
-        bounding box (x_min, x_max, y_min, y_max, z_min, z_max) the density is 0."""
+        bounding box (x_min, x_max, y_min, y_max, z_min, z_max) the density is 0.  `grid` (occupancy.OccupancyGrid, tuned
+        networks only): the density kernel runs only at the samples the grid lists, every other sample is 0 — the same
+        bits wherever no skipped sample has a density; the last sample of every ray is re-evaluated as without it."""
         pref = 'fine_' if use_fine else 'coarse_'
         if not self.tuned:
+            if grid is not None:
+                from ..occupancy import require_tuned
+                require_tuned(self)
             sigma = torch.relu(self._sigma_generic(rayo, rayd, z, pref)[0])
         else:
-            raw = ops.nerf_sigma_fwd(rayo, rayd, z, self._nerf_geom_blob(pref), self.precision)
-            sigma = torch.relu(self._refine_last_sigma(rayo, rayd, z, raw, pref))
+            sigma = self._sigma_tuned(rayo, rayd, z, pref, bbox, grid)
+            if grid is not None and grid.check_due(pref):
+                grid.verify(sigma, self._sigma_tuned(rayo, rayd, z, pref, bbox, None), pref)
+            return sigma
+        if bbox is not None:
+            sigma = sigma * self._in_bounds(rayo, rayd, z, bbox)
+        return sigma
+
+    def _sigma_tuned(self, rayo, rayd, z, pref, bbox, grid):
+        blob = self._nerf_geom_blob(pref)
+        if grid is None:
+            raw = ops.nerf_sigma_fwd(rayo, rayd, z, blob, self.precision)
+        else:
+            raw = grid.sigma_raw(rayo, rayd, z, pref, blob, self.precision, bbox)
+        sigma = torch.relu(self._refine_last_sigma(rayo, rayd, z, raw, pref))
         if bbox is not None:
             sigma = sigma * self._in_bounds(rayo, rayd, z, bbox)
         return sigma

@@ -5,6 +5,7 @@ buffers on disk:
         --ckpt=<nerfactor outdir>/checkpoints/ckpt-N --trained_nerf=<nerf outdir> \\
         [--color_correct_albedo] [--tgt_albedo ...] [--tgt_brdf ...] [--sv_axis_i/min/max] \\
         [--scene_bbox x0,x1,y0,y1,z0,z1] [--occu_thres 0] [--mlp_chunk ...] [--split test] [--debug]
+        [--occupancy_grid R [--grid_margin 10] [--grid_dilate 2] [--grid_probes 4] [--grid_check K]]
 
 For every shape_mode but 'nerf' NeRFactor's test-mode call reads only alpha, xyz and rayo of the surface buffers; those
 are marched per view from the NeRF (nerfactor/surface.py: geometry_from_nerf's march ending in nfx_nerf_surface_fwd) —
@@ -12,7 +13,8 @@ no depth gradient, no normals, no shadow rays, no 1.3 GB lvis.npy per 800 x 800 
 /metadata.json of the NeRFactor config, rays at its imh; the NeRF checkpoint is the latest under --trained_nerf.  The
 editing / relighting flags mean what they mean in test.py (probes on every view, OLAT on the last); images go to
 <outdir>/vis_test/ckpt-N_from_nerf[_<edit>]/batch%09d/.  With N ranks each rank marches and renders only its contiguous
-ray range of every view; uint8 rows travel to rank 0 (util/shard.py)."""
+ray range of every view; uint8 rows travel to rank 0 (util/shard.py).  --occupancy_grid R: the march's density passes
+evaluate only the samples an R^3 grid baked from the NeRF lists (occupancy.py; geometry_from_nerf's flags)."""
 import argparse
 import glob
 import json
@@ -23,7 +25,7 @@ import numpy as np
 import torch
 
 from .. import dist as nfx_dist
-from . import models
+from . import models, occupancy
 from . import test as test_driver
 from .datasets.nerf import gen_rays
 from .geometry_from_nerf import latest_checkpoint
@@ -49,6 +51,7 @@ def parse_args(argv=None):
     ap.add_argument('--mlp_chunk', type=int, default=1 << 25, help="density samples per kernel launch")
     ap.add_argument('--split', default='test', help="cameras: <data_root>/<split>_???")
     ap.add_argument('--debug', action='store_true')
+    occupancy.add_arguments(ap)
     return ap.parse_args(argv)
 
 
@@ -106,11 +109,13 @@ def main(argv=None):
     config = configutil.read_config(config_ini)
     check_config(config)
     bbox = parse_bbox(args.scene_bbox)
+    occupancy.check_arguments(args)
     if not torch.cuda.is_available():
         raise RuntimeError("render_from_nerf needs an MI355X: libnfx has no CPU path")
     device = nfx_dist.local_device()
     rank, ws = nfx_dist.init_from_env(device=device)
     nerf_model, nerf_config = load_nerf(args.trained_nerf, device)
+    grid = occupancy.from_arguments(args, nerf_model, bbox, config.get('DEFAULT', 'data_root'))
     model = models.get_model_class(config.get('DEFAULT', 'model'))(config, debug=args.debug).to(device)
     configutil.restore_model(model, args.ckpt)
     model.to(device)
@@ -124,7 +129,8 @@ def main(argv=None):
             rayo = torch.from_numpy(rayo[lo:hi]).to(device)
             rayd = torch.from_numpy(rayd[lo:hi]).to(device)
             alpha, xyz = march_surface(nerf_model, rayo, rayd, nerf_config, bbox=bbox, occu_thres=args.occu_thres,
-                                       mlp_chunk=args.mlp_chunk)
+                                       mlp_chunk=args.mlp_chunk, grid=grid)
+            occupancy.log_view(grid, id_, 'render_from_nerf')
             test_driver.render_test_view(model, nerfactor_test_batch(id_, hw, rayo, rayd, alpha, xyz),
                                          join(outroot, 'batch{i:09d}'.format(i=batch_i)), args,
                                          relight_olat=batch_i == len(metas) - 1, albedo_scales=albedo_scales,

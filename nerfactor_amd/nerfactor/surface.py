@@ -15,13 +15,14 @@ from .geometry_from_nerf import _sample_counts
 
 
 def march_surface(nerf_model, rayo, rayd, config, bbox=None, occu_thres=0., mlp_chunk=1 << 25, quantize_alpha=True,
-                  full=False):
+                  full=False, grid=None):
     """(alpha[n], xyz[n, 3]) of the rays rayo + t rayd, as geometry_from_nerf writes them to alpha.png / xyz.npy.
 
     `config` is the NeRF's own (near, far, sample counts, lin_in_disp); `bbox` (x_min, x_max, ..., z_max) zeroes the
     density outside it, as in geometry_from_nerf.  quantize_alpha: alpha as alpha.png read back gives it
     (floor(255 alpha + 0.5) / 255); xyz always carries the unquantised alpha, as xyz.npy does.
-    full = True: (alpha, xyz, occu, depth) with the raw occupancy and expected depth of compute_depth_and_normal."""
+    full = True: (alpha, xyz, occu, depth) with the raw occupancy and expected depth of compute_depth_and_normal.
+    grid (occupancy.OccupancyGrid): both density passes evaluate only the samples it lists."""
     n_coarse, n_fine, lin_in_disp = _sample_counts(config)
     near, far = config.getfloat('DEFAULT', 'near'), config.getfloat('DEFAULT', 'far')
     rays_per_call = max(1, mlp_chunk // (n_coarse + n_fine))       # compute_depth_and_normal's chunking
@@ -37,9 +38,9 @@ def march_surface(nerf_model, rayo, rayd, config, bbox=None, occu_thres=0., mlp_
         o, d = rayo[lo:hi].contiguous(), rayd[lo:hi].contiguous()
         # geometry_from_nerf._march: coarse pass, importance samples, fine densities
         z = nerf_model.gen_z(near, far, n_coarse, o.shape[0], lin_in_disp=lin_in_disp, perturb=False, device=o.device)
-        w = nerf_model.accumulate_sigma(nerf_model.eval_sigma(o, d, z, use_fine=False, bbox=bbox), z, d)
+        w = nerf_model.accumulate_sigma(nerf_model.eval_sigma(o, d, z, use_fine=False, bbox=bbox, grid=grid), z, d)
         z = nerf_model.gen_z_fine(z, w, n_fine, perturb=False)
-        sigma = nerf_model.eval_sigma(o, d, z, use_fine=True, bbox=bbox)
+        sigma = nerf_model.eval_sigma(o, d, z, use_fine=True, bbox=bbox, grid=grid)
         a, x, dep, occ = ops.nerf_surface(sigma, z, o, d, occu_thres=occu_thres, quantize_alpha=quantize_alpha,
                                           want_occu=full)
         alpha[lo:hi] = a

@@ -1038,6 +1038,95 @@ def nerf_sigma_grad(rayo, rayd, z, geom_blob, prec='bf16'):
                                       _stream()), 'nfx_nerf_sigma_grad')
     return out[..., :3], out[..., 3]
 
+
+# ------------------------------------------------------------------------------ occupancy grid
+OCCGRID_MAX_RES, OCCGRID_MAX_PROBES = 1024, 1 << 30     # nfx.h: NFX_OCCGRID_MAX_RES, NFX_OCCGRID_MAX_PROBES
+
+
+def _box6(box, name):
+    box = [float(x) for x in box]
+    if len(box) != 6:
+        raise _capi.NfxError("%s: (x_min, x_max, y_min, y_max, z_min, z_max)" % name)
+    return (ctypes.c_float * 6)(*box)
+
+
+def occgrid_workspace(n_rays, n_samples, device):
+    """The int32 workspace of occgrid_select for n_rays x n_samples samples."""
+    nbytes = lib.nfx_occgrid_workspace_bytes(n_rays, n_samples)
+    return torch.empty((max(nbytes, 16) // 4,), dtype=torch.int32, device=device)
+
+
+def occgrid_list(ws, n_pts):
+    """(list[n_pts], count[1]) views of an occgrid_select workspace: the ascending flat sample indices and their number
+    (list[count:] is not written)."""
+    first = 4 + ((n_pts + 1023) // 1024 + 3) // 4 * 4
+    return ws[first:first + n_pts], ws[:1]
+
+
+def occgrid_select(rayo, rayd, z, bits, res, box, bbox=None, out=None, ws=None):
+    """(out[N, S], list, count): lists the samples rayo + rayd z that lie outside the grid's box or in a set cell of
+    `bits` (int32 [ceil(res^3 / 32)], nfx.h's layout) and inside the optional scene bbox, and writes 0.0 to `out` at every
+    other sample.  The list stays on the device."""
+    rayo = _dev(rayo, 'rayo', (None, 3))
+    n = rayo.shape[0]
+    rayd = _dev(rayd, 'rayd', (n, 3))
+    z = _dev(z, 'z', (n, None))
+    s = z.shape[1]
+    if not (bits.is_cuda and bits.dtype == torch.int32 and bits.is_contiguous() and bits.numel() == (res ** 3 + 31) // 32):
+        raise _capi.NfxError("occgrid_select: bits must be a contiguous CUDA int32 tensor of ceil(res^3 / 32) words")
+    if out is None:
+        out = torch.empty((n, s), dtype=torch.float32, device=z.device)
+    if ws is None:
+        ws = occgrid_workspace(n, s, z.device)
+    lst, count = occgrid_list(ws, n * s)
+    if n == 0:
+        count.zero_()
+        return out, lst, count
+    check(lib.nfx_occgrid_select(_ptr(rayo), _ptr(rayd), _ptr(z), n, s, _ptr(bits), int(res), _box6(box, 'box'),
+                                 None if bbox is None else _box6(bbox, 'bbox'), _ptr(out), _ptr(ws), ws.numel() * 4,
+                                 _stream()), 'nfx_occgrid_select')
+    return out, lst, count
+
+
+def nerf_sigma_fwd_list(rayo, rayd, z, blob, lst, count, out, prec='bf16'):
+    """out[N, S] at the flat sample indices lst[0 .. count[0]) = nerf_sigma_fwd's values there (in place; every other
+    sample is left alone).  The count is read on the device."""
+    rayo, rayd, z, n, s = _ray_args(rayo, rayd, z, blob)
+    out = _dev(out, 'out', (n, s))
+    for t, name in ((lst, 'list'), (count, 'count')):
+        if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+            raise _capi.NfxError("nerf_sigma_fwd_list: %s must be a contiguous CUDA int32 tensor" % name)
+    check(lib.nfx_nerf_sigma_fwd_list(_ptr(rayo), _ptr(rayd), _ptr(z), n, s, _ptr(blob), _PREC[prec], _ptr(lst),
+                                      _ptr(count), _ptr(out), _stream()), 'nfx_nerf_sigma_fwd_list')
+    return out
+
+
+def nerf_sigma_fwd_grid(rayo, rayd, z, blob, bits, res, box, bbox=None, prec='bf16'):
+    """(sigma_raw[N, S], count[1]): nerf_sigma_fwd evaluated only at the samples occgrid_select lists, 0.0 at the others;
+    count = how many were evaluated (int32, on the device)."""
+    out, lst, count = occgrid_select(rayo, rayd, z, bits, res, box, bbox)
+    nerf_sigma_fwd_list(rayo, rayd, z, blob, lst, count, out, prec)
+    return out, count
+
+
+def occgrid_bake(probe_sigma, res, probes, margin=0., dilate=1):
+    """The grid's bits (int32 [ceil(res^3 / 32)]) from the raw densities of the (res probes)^3 probe lattice (nfx.h:
+    nfx_occgrid_bake): a cell is occupied when a probe has sigma_raw > -margin, then dilated by `dilate` cells."""
+    m = res * probes
+    if not (1 <= res <= OCCGRID_MAX_RES and 1 <= probes <= 16 and m ** 3 <= OCCGRID_MAX_PROBES and 0 <= dilate <= 16):
+        raise _capi.NfxError("occgrid_bake: res = %d, probes = %d, dilate = %d (1 <= res <= %d, 1 <= probes <= 16, "
+                             "(res probes)^3 <= %d, 0 <= dilate <= 16)" % (res, probes, dilate, OCCGRID_MAX_RES,
+                                                                         OCCGRID_MAX_PROBES))
+    probe_sigma = _dev(probe_sigma, 'probe_sigma')
+    if probe_sigma.numel() != m ** 3:
+        raise _capi.NfxError("occgrid_bake: %d probe densities, expected (res probes)^3 = %d" % (probe_sigma.numel(), m ** 3))
+    bits = torch.empty(((res ** 3 + 31) // 32,), dtype=torch.int32, device=probe_sigma.device)
+    ws = torch.empty_like(bits)
+    check(lib.nfx_occgrid_bake(_ptr(probe_sigma), int(res), int(probes), float(margin), int(dilate), _ptr(bits), _ptr(ws),
+                               _stream()), 'nfx_occgrid_bake')
+    return bits
+
+
 def amsgrad_step(p, g, m, v, vhat, lr, step, beta1=0.9, beta2=0.999, eps=1e-7):
     """In-place Keras Adam(amsgrad=True) update of the flat fp32 buffer `p` (step is 1-based)."""
     for t in (p, g, m, v, vhat):
