@@ -10,7 +10,7 @@ import torch  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libnfx.so')
-if os.environ.get('NFX_LIB_PATH'):   # experiment builds (python -m nerfactor_amd.build --out ...)
+if os.environ.get('NFX_LIB_PATH'):   # a second library (python -m nerfactor_amd.build --out ...)
     LIB_PATH = os.environ['NFX_LIB_PATH']
 
 PREC_BF16, PREC_FP32, PREC_FP32_NATIVE = 0, 1, 2    # (PREC_FP32_NATIVE: the runtime-shaped kernels only)

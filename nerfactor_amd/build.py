@@ -23,12 +23,10 @@ HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 # multiply-adds appear only where written as fmaf().
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fPIC', '-fvisibility=hidden',
          '-Wno-unused-result', '-I' + os.path.join(ROOT, 'include')]
-if os.environ.get('NFX_EXTRA_DEFS'):  # experiment switches, e.g. NFX_EXTRA_DEFS='-DNFX_V5_BIAS_COPY'
-    FLAGS += os.environ['NFX_EXTRA_DEFS'].split()
 
 
 # Per-source extra flags.  -amdgpu-mfma-vgpr-form: MFMA accumulators in ArchVGPRs (the epilogue reads them without
-# v_accvgpr_read; activations move to AccVGPRs, which MFMA takes as B operands).  NFX_VGPR_FORM_FILES overrides the list.
+# v_accvgpr_read; activations move to AccVGPRs, which MFMA takes as B operands).
 VGPR_FORM = ['-mllvm', '-amdgpu-mfma-vgpr-form']
 # r01: lvis 21.16 -> 20.79 ms, NeRF render 1228 -> 1239 TFLOP/s (instruction count of the lvis kernel 5380 -> 4554),
 # variant 6 1293 -> 1330 TFLOP/s, density-gradient kernel 72.5 -> 68.4 ms per 256 x 256 view; no effect on the
@@ -43,10 +41,6 @@ VGPR_FORM = ['-mllvm', '-amdgpu-mfma-vgpr-form']
 FAST_DIV = ['-fno-hip-fp32-correctly-rounded-divide-sqrt']
 PER_FILE_FLAGS = {'lvis_v2.hip': VGPR_FORM, 'nerf_mlp_v6.hip': VGPR_FORM, 'nerf_sigma_v6.hip': VGPR_FORM,
                   'nerf_geom.hip': VGPR_FORM, 'mlp128_bwd_fused.hip': VGPR_FORM, 'shade.hip': FAST_DIV}
-if os.environ.get('NFX_VGPR_FORM_FILES') is not None:      # A/B experiment libraries: only the VGPR-form entries are overridden —
-    # shade.hip keeps FAST_DIV, so an experiment build divides exactly like the shipped library
-    PER_FILE_FLAGS = dict({f: v for f, v in PER_FILE_FLAGS.items() if v is not VGPR_FORM},
-                          **{f: VGPR_FORM for f in os.environ['NFX_VGPR_FORM_FILES'].split(',') if f})
 
 
 def _sources():
@@ -68,7 +62,7 @@ def _job(src, force):
         if line.startswith('#include "') and line.rstrip().endswith('.hip"'):
             newest = max(newest, os.path.getmtime(os.path.join(CSRC, line.split('"')[1])))
     cmd = [HIPCC] + FLAGS + PER_FILE_FLAGS.get(src, []) + ['-x', 'hip', '-c', spath, '-o', obj]
-    stamp = obj + '.cmd'     # the command line is part of the staleness check (per-file flags, NFX_EXTRA_DEFS)
+    stamp = obj + '.cmd'     # the command line is part of the staleness check (per-file flags)
     same_cmd = os.path.exists(stamp) and open(stamp).read() == ' '.join(cmd)
     return src, obj, cmd, force or not (same_cmd and os.path.exists(obj) and os.path.getmtime(obj) >= newest)
 
@@ -88,7 +82,8 @@ def _compile(job, verbose):
 
 
 def build(force=False, verbose=False, out=None):
-    """out: alternative .so path (experiment builds with NFX_EXTRA_DEFS; objects go to build/obj_<name>)."""
+    """out: alternative .so path (a second library, e.g. of another checkout, loaded with NFX_LIB_PATH; objects go to
+    build/obj_<name>)."""
     global OBJDIR, LIB
     if out:
         LIB = os.path.abspath(out)

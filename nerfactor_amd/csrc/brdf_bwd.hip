@@ -47,8 +47,6 @@ __device__ __forceinline__ void dgrad_layer(WStream& ws, int tid, const bf16x8 (
             const float hv = (float)hact[2 * t + (r >> 3)][0][r & 7];
             dout[2 * t + (r >> 3)][0][r & 7] = (__bf16)(hv > 0.f ? acc[0][r] : 0.f);
         }
-        mfma_operand_fence(dout[2 * t][0]);
-        mfma_operand_fence(dout[2 * t + 1][0]);
     });
 }
 
@@ -152,7 +150,6 @@ __global__ __launch_bounds__(kNW * 64, 1) void brdf_spec_bwd_kernel(
         for (int s = 0; s < 2; ++s) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) bin[s][0][j] = (__bf16)v[8 * s + j];
-            mfma_operand_fence(bin[s][0]);
         }
         // ---- forward (re-computed)
         bf16x8 h0[8][1], h1[8][1], h2[8][1], h3[8][1];
@@ -181,8 +178,6 @@ __global__ __launch_bounds__(kNW * 64, 1) void brdf_spec_bwd_kernel(
                 const float hv = (float)h3[2 * t + (r >> 3)][0][r & 7];
                 dz3[2 * t + (r >> 3)][0][r & 7] = (__bf16)(hv > 0.f ? acc[0][r] : 0.f);
             }
-            mfma_operand_fence(dz3[2 * t][0]);
-            mfma_operand_fence(dz3[2 * t + 1][0]);
         });
         f32x16 dx[1];  // gradient w.r.t. the 32 input slots of this lane's half: reg r <-> (s = r>>3, j = r&7)
         tile_init<8, 0, 2, kNW>(ws, tid, [&](f32x16(&a)[1]) { zero_acc<1>(a); }, dz3, dz3, dx);   // W3[128:, :] dZ3
@@ -358,7 +353,6 @@ __global__ __launch_bounds__(kNW * 64, 1) void brdf_rows_kernel(
         for (int s = 0; s < 2; ++s) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) bin[s][0][j] = (__bf16)v[8 * s + j];
-            mfma_operand_fence(bin[s][0]);
         }
         bf16x8 h0[8][1], h1[8][1], h2[8][1], h3[8][1];
         layer<2, 0, 4, 1, 2, true, kNW>(ws, tid, bias_lds, bin, bin, h0);
@@ -419,8 +413,6 @@ __global__ __launch_bounds__(kNW * 64, 1) void brdf_rows_kernel(
                     const float hv = (float)h3[2 * t + (r >> 3)][0][r & 7];
                     dz3[2 * t + (r >> 3)][0][r & 7] = (__bf16)(hv > 0.f ? acc[0][r] : 0.f);
                 }
-                mfma_operand_fence(dz3[2 * t][0]);
-                mfma_operand_fence(dz3[2 * t + 1][0]);
             });
             store_hidden<8>(fs, kOffDZ + 384, h, dz3);
             f32x16 dx[1];  // gradient w.r.t. the 32 input slots of this lane's half

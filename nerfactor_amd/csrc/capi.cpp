@@ -270,7 +270,7 @@ int nfx_nerf_mlp_fwd(const float* rayo, const float* rayd, const float* z, int64
         // next tile's MFMAs, weight stream by LDS-DMA into a 6-slot ring (nerf_mlp_v6.hip); 6 / 8 = the same kernel
         // with register-staged weights (one / two staging sets); 1 = the 8 waves x 32 points reference geometry with
         // two waves per SIMD, 0 = 4 x 64 plain (nerf_mlp.hip).  All bit-identical.  The intermediate variants 2, 3, 5
-        // of r01 live in scripts/experiments/ (not built).
+        // of r01 are in the git history (not built).
         const int variant = env_int("nerf_variant", 7);
         if (variant == 8)
             return hip_result(nfx_launch_nerf_mlp_bf16_v6(rayo, rayd, z, n_pts, n_samples, blob, rgbs, blocks, 2,

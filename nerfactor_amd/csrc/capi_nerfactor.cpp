@@ -304,9 +304,7 @@ int nfx_brdf_spec_fwd(const float* xyz, const float* cam, const float* normal, c
     int variant = nfx_option_int("brdf_variant", 6);
     if (variant >= 5) {
         int ct = nfx_option_int("brdf_ct", 4);
-#ifndef NFX_EXPERIMENT_BUILD
         if (ct == 8 && variant != 6) ct = 2;   // <2, 0, 8> is not built
-#endif
         int rc = nfx_launch_brdf_spec_v3(xyz, cam, normal, z, z_dim, lxyz, n_lights, blob, n, spec, ct, variant == 6,
                                          nfx_option_int("m128_blocks", 256), (hipStream_t)stream);
         if (rc == -1 && ct == 8)   // more lights than the 8-wave row queues hold: the 4-wave form

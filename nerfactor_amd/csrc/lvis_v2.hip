@@ -13,14 +13,6 @@
 #include "mlp128_layout.hpp"
 #include "mlp_engine.hpp"
 
-
-#ifdef NFX_XP_TRANS_LOAD
-#ifdef NFX_XP_LOAD_PLAIN_VALU     // control: full-rate VALU instructions of the same total issue time instead of transcendental ones
-#define NFX_XP_LOAD_INSN "v_mul_f32 %0, 1.0, %0\n\tv_mul_f32 %0, 1.0, %0\n\tv_mul_f32 %0, 1.0, %0\n\tv_mul_f32 %0, 1.0, %0"
-#else
-#define NFX_XP_LOAD_INSN "v_sin_f32 %0, %0"
-#endif
-#endif
 namespace nfx {
 namespace lv2 {
 
@@ -53,8 +45,6 @@ __device__ __forceinline__ void cvt_pair(float v0, float v1, bf16x8& dst, int j)
         w = __builtin_elementwise_max(w, z);
         pr = __builtin_bit_cast(b2, w);
     }
-    // (the converted pair is an MFMA operand of the next layer: mlp_engine.hpp, "MFMA operands written by packed ...")
-    pr = __builtin_bit_cast(b2, mfma_operand_dword(__builtin_bit_cast(unsigned, pr)));
     dst[j] = pr[0];
     dst[j + 1] = pr[1];
 }
@@ -86,7 +76,7 @@ struct InitBias {   // broadcast LDS reads of the bias tile
     template <int CT>
     __device__ __forceinline__ void operator()(int lane, Acc<CT>& acc) const {
         // one read group, the other column tiles' accumulators by register copy (accumulators are ArchVGPRs here):
-        // light-visibility kernel 17.57 -> 17.1 ms on r01; NFX_LV2_BIAS_READS restores one read group per column tile
+        // light-visibility kernel 17.57 -> 17.1 ms on r01 against one read group per column tile
         const float* bt = bias_tile + 4 * (lane >> 5);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -304,14 +294,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void resident128_kernel(Args a) {
                 const float inv = 1.0f / sqrtf(fmaxf(sq, 1e-6f));
 #pragma unroll
                 for (int k = 0; k < 3; ++k) d[k] *= inv;
-#ifdef NFX_XP_TRANS_LOAD
-                {
-                    float tl = d[0];
-#pragma unroll
-                    for (int i = 0; i < NFX_XP_TRANS_LOAD; ++i) asm volatile(NFX_XP_LOAD_INSN : "+v"(tl));
-                    asm volatile("" ::"v"(tl));
-                }
-#endif
                 posenc<4, CT>(d, h, c, pl);
                 pre_pt[c] = a.pre + pt * 256;
                 front[c] = true;
@@ -344,7 +326,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void resident128_kernel(Args a) {
                 for (int sidx = 0; sidx < 2; ++sidx) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) pl[sidx][c][j] = (__bf16)v[8 * sidx + j];
-                    mfma_operand_fence(pl[sidx][c]);
                 }
                 pre_pt[c] = nullptr;
             }
@@ -430,12 +411,9 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void resident128_kernel(Args a) {
 // ring of queued rows per wave: 1024 entries of 16 bits = (point slot << 10) | light, point slot = local point index
 // mod 8 (a pass decodes it against the index of the newest filled point; the fill loop never lets the queue span 8
 // points).  2 KiB per wave: 8 waves (two per SIMD) fit next to the network.
-#ifndef NFX_BRDF_SWAP
-#define NFX_BRDF_SWAP 1   // 1 ds_bpermute (default) | 0 __builtin_amdgcn_permlane32_swap | 2 hand-timed asm: brdf_compact_kernel's header
-#endif
 constexpr int kRing = 1024;
 typedef unsigned short ring_t;
-// queue geometry per wave: ring entries and point slots.  4 waves: 1024 entries, 8 slots.  8 waves (experiment form):
+// queue geometry per wave: ring entries and point slots.  4 waves: 1024 entries, 8 slots.  8 waves (two per SIMD):
 // 704 entries (>= 64 - 1 + 512 lights), 4 slots — what fits beside the network, the lights and the point tables
 template <int NW> struct Queue {
     static constexpr int kCap = NW == 8 ? 704 : kRing, kSlots = NW == 8 ? 4 : 8;
@@ -568,7 +546,7 @@ __device__ __forceinline__ void brdf_row_inputs(const float (&x)[3], const float
 // The closed-form geometry of ONE (point, light) row (brdf_point_frame + brdf_row_angles) with the values of BOTH lane halves: S[q] is what the half-0 lane
 // of the row's column puts into input slot q (sines, phi_d, theta_h), C[q] what the half-1 lane does (cosines, theta_d;
 // slot 7 of half 1 is z_0, loaded by the caller).  brdf_compact_kernel lets the half-0 lane of column p compute the row
-// of column tile 2k and the half-1 lane the row of tile 2k + 1, and swaps halves with v_permlane32_swap: each lane
+// of column tile 2k and the half-1 lane the row of tile 2k + 1, and swaps halves (one exchange per slot): each lane
 // runs the geometry of CT / 2 rows instead of CT (the two halves used to compute the same row twice).
 __device__ __forceinline__ void nrm_rsq(float (&v)[3]) {
     const float inv = __builtin_amdgcn_rsqf(fmaxf(dot3(v, v), 1e-6f));
@@ -640,31 +618,18 @@ __device__ __forceinline__ void brdf_row_angles(const float (&x)[3], const float
 // lanes of the second column tile, different from run to run) and did not find out why.  Round 3 did: the exchange of
 // the two lane halves' geometry by v_permlane32_swap_b32.  With a partner wave on the SIMD the swap reads operands a
 // VALU instruction wrote two wait states earlier before they have landed — with the hand-placed `s_nop 1` of rounds
-// 1-2 (NFX_BRDF_SWAP=2: 11 000 rows of 10^8 wrong per call) AND with the compiler's own
-// __builtin_amdgcn_permlane32_swap, whose hazard recogniser places the same two wait states (NFX_BRDF_SWAP=0: 2 200
-// rows).  Through ds_bpermute (NFX_BRDF_SWAP=1, the default: the LDS crossbar, counted by lgkmcnt) the 8-wave kernel is
-// bit-identical to the 4-wave one on every call (scripts/brdf_nw8_soak.py).  One wave per SIMD never showed the fault
+// 1-2 (hand-timed asm: 11 000 rows of 10^8 wrong per call) AND with the compiler's own
+// __builtin_amdgcn_permlane32_swap, whose hazard recogniser places the same two wait states (2 200 rows).  Through
+// ds_bpermute (__shfl_xor, the form that ships: the LDS crossbar, counted by lgkmcnt) the 8-wave kernel is
+// bit-identical to the 4-wave one on every call (scripts/soak_8wave.py).  One wave per SIMD never showed the fault
 // (10^10 rows in round 2), but the shipped form does not depend on those wait states any more.
-#ifdef NFX_XP_VGPR_CAP      // round-6 experiment: the two-waves-per-SIMD forms may not touch the top of their half of the register file
-#define NFX_XP_CAP_ATTR __attribute__((amdgpu_num_vgpr(NFX_XP_VGPR_CAP)))      // (an integer constant: every instantiation; the one-wave reference forms spill, slower but the same sums)
-#else
-#define NFX_XP_CAP_ATTR
-#endif
 template <int CT, int GEO, int NW>
-__global__ __launch_bounds__(NW * 64, NW / 4) NFX_XP_CAP_ATTR void brdf_compact_kernel(Args a) {
+__global__ __launch_bounds__(NW * 64, NW / 4) void brdf_compact_kernel(Args a) {
     constexpr int kNW = NW;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using namespace m128;
     const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, p = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: point indices and ring base live in SGPRs
-#ifdef NFX_XP_FORCE_SCRATCH
-    // round-6 experiment: the failing <2, 0, 8> is the ONLY kernel of the library whose register
-    // allocation spills to SCRATCH MEMORY (private_segment_fixed_size 20: the lane half h, stored once and re-loaded in every
-    // pass, and a constant pair).  This build gives the healthy <2, 1, 8> the same thing: h goes through a private slot.
-    volatile int xp_slot[4];
-    xp_slot[0] = h;
-    xp_slot[2] = 0x3f317218;
-#endif
     {   // the whole network, once
         const u32x4* src = reinterpret_cast<const u32x4*>(a.blob);
         u32x4* dst = reinterpret_cast<u32x4*>(smem);
@@ -705,29 +670,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) NFX_XP_CAP_ATTR void brdf_compact_
                 nr[k] = a.normal[pt * 3 + k];
             }
             world2local(nr, rot);
-#ifdef NFX_XP_LDS_INPUTS
-            // round-6 experiment: the GEO = 0 pass takes its per-point inputs from the wave's LDS table instead of per-lane
-            // global loads (x, cam, normal, z: raw values, the per-row op sequence unchanged) — no vector-memory LOAD inside a pass
-            if constexpr (!kPark) {
-                float cmx[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) cmx[k] = a.cam[pt * 3 + k];
-                const float* zp = a.z + pt * a.z_dim;
-                float zv[17];
-#pragma unroll
-                for (int i = 0; i < 17; ++i) zv[i] = i < a.z_dim ? zp[i] : 0.0f;
-                if (lane == 0) {
-                    f32x4* ps = reinterpret_cast<f32x4*>(ptab + (int)(kfill & (kSlots - 1)) * 32);
-                    ps[0] = f32x4{x[0], x[1], x[2], cmx[0]};
-                    ps[1] = f32x4{cmx[1], cmx[2], nr[0], nr[1]};
-                    ps[2] = f32x4{nr[2], zv[0], zv[1], zv[2]};
-                    ps[3] = f32x4{zv[3], zv[4], zv[5], zv[6]};
-                    ps[4] = f32x4{zv[7], zv[8], zv[9], zv[10]};
-                    ps[5] = f32x4{zv[11], zv[12], zv[13], zv[14]};
-                    ps[6] = f32x4{zv[15], zv[16], 0.f, 0.f};
-                }
-            }
-#endif
             if constexpr (kPark) {
                 float cm[3], prot[9], pvl[3];
 #pragma unroll
@@ -801,7 +743,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) NFX_XP_CAP_ATTR void brdf_compact_
             orow[c] = ok ? rpt[c] * L + rl[c] : -1;
         }
         if constexpr (GEO == 1 && CT % 2 == 0) {
-            // lane half h runs the geometry of the row of column tile 2k + h; one v_permlane32_swap per input slot
+            // lane half h runs the geometry of the row of column tile 2k + h; one lane-half exchange per input slot
             // hands each half its own values of both rows (brdf_row_angles; the per-point half comes from the table)
 #pragma unroll
             for (int k2 = 0; k2 < CT; k2 += 2) {
@@ -811,15 +753,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) NFX_XP_CAP_ATTR void brdf_compact_
                 const float x[3] = {q0[0], q0[1], q0[2]}, vl[3] = {q0[3], q1[0], q1[1]};
                 const float rot[9] = {q1[2], q1[3], q2[0], q2[1], q2[2], q2[3], q3[0], q3[1], q3[2]};
                 const float lp[3] = {lx[l * 3], lx[l * 3 + 1], lx[l * 3 + 2]};
-#ifdef NFX_XP_TRANS_LOAD      // round-6 experiment: the healthy two-wave kernels under a partner that issues MANY quarter-rate
-                              // transcendental instructions (what the failing <2, 0, 8> has five times more of): dead work, same outputs
-                {
-                    float tl = lp[0];
-#pragma unroll
-                    for (int i = 0; i < NFX_XP_TRANS_LOAD; ++i) asm volatile(NFX_XP_LOAD_INSN : "+v"(tl));
-                    asm volatile("" ::"v"(tl));
-                }
-#endif
                 float S[8], C[8];
                 brdf_row_angles(x, lp, rot, vl, S, C);
                 float v[2][16];
@@ -829,19 +762,10 @@ __global__ __launch_bounds__(NW * 64, NW / 4) NFX_XP_CAP_ATTR void brdf_compact_
                     //   first  = [S(row 2k) ; C(row 2k)]     = slot q of column tile 2k for both halves
                     //   second = [S(row 2k+1) ; C(row 2k+1)] = slot q of column tile 2k + 1
                     float first = S[q], second = C[q];
-#if NFX_BRDF_SWAP == 1      // the exchange through ds_bpermute (LDS crossbar, counted by lgkmcnt)
+                    // the exchange through ds_bpermute (LDS crossbar, counted by lgkmcnt), not v_permlane32_swap: the kernel's header
                     const float recv = __shfl_xor(h ? first : second, 32, 64);
                     first = h ? recv : first;
                     second = h ? second : recv;
-#elif NFX_BRDF_SWAP == 2    // rounds 1-2: hand-timed wait states — WRONG with a partner wave on the SIMD (see the kernel's header)
-                    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 0" : "+v"(first), "+v"(second));
-#else                       // the compiler's own v_permlane32_swap (its hazard recogniser places the wait states)
-                    {
-                        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(first), __float_as_uint(second), false, false);
-                        first = __uint_as_float(sw[0]);
-                        second = __uint_as_float(sw[1]);
-                    }
-#endif
                     v[0][q] = first;
                     v[1][q] = second;
                 }
@@ -849,16 +773,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) NFX_XP_CAP_ATTR void brdf_compact_
                 for (int cc = 0; cc < 2; ++cc) {
                     // the latent code of the row's point: z_0 (slot 7 of half 1) and this half's z_{1 + 2j + h}
                     const f32x4* pz = reinterpret_cast<const f32x4*>(ptab + rslot[k2 + cc] * 32);
-#ifdef NFX_XP_USE_V255
-                    // round-6 experiment: the healthy <2, 1, 8> made to keep a live value in v255 (its allocation stops at v246)
-                    int hs;
-                    asm volatile("v_mov_b32 v255, %1\n\ts_nop 4\n\tv_mov_b32 %0, v255" : "=v"(hs) : "v"(h) : "v255");
-#elif defined(NFX_XP_FORCE_SCRATCH)
-                    const int hs = xp_slot[0];          // h, re-loaded from scratch memory
-                    xp_slot[2] = xp_slot[2] + cc;       // and a slot that is re-stored in the loop, like the spilled constant pair
-#else
                     const int hs = h;
-#endif
                     const f32x4 za = pz[4 + 2 * hs], zb = pz[5 + 2 * hs];
                     if (hs) v[cc][7] = pz[3][3];
 #pragma unroll
@@ -870,7 +785,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) NFX_XP_CAP_ATTR void brdf_compact_
                     for (int sidx = 0; sidx < 2; ++sidx) {
 #pragma unroll
                         for (int j = 0; j < 8; ++j) pl[sidx][k2 + cc][j] = (__bf16)v[cc][8 * sidx + j];
-                        mfma_operand_fence(pl[sidx][k2 + cc]);
                     }
                 }
             }
@@ -880,17 +794,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) NFX_XP_CAP_ATTR void brdf_compact_
                 const long long pt = rpt[c];
                 const int l = rl[c];
                 float x[3], lp[3], cm[3], nr[3];
-#ifdef NFX_XP_LDS_INPUTS
-                const float* row = ptab + rslot[c] * 32;
-                const float* zsrc = row + 9;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    x[k] = row[k];
-                    lp[k] = lx[l * 3 + k];
-                    cm[k] = row[3 + k];
-                    nr[k] = row[6 + k];
-                }
-#else
                 const float* zsrc = a.z + pt * a.z_dim;
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
@@ -899,28 +802,15 @@ __global__ __launch_bounds__(NW * 64, NW / 4) NFX_XP_CAP_ATTR void brdf_compact_
                     cm[k] = a.cam[pt * 3 + k];
                     nr[k] = a.normal[pt * 3 + k];
                 }
-#endif
                 float v[16];
-#ifdef NFX_XP_NOSCRATCH
-                // round-6 experiment: <2, 0, 8> without its scratch spill — the lane half is re-derived where it is used
-                // (a volatile asm is neither hoisted nor kept live across the pass), so nothing has to be spilled for it
-                int hx;
-                asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0\n\tv_lshrrev_b32 %0, 5, %0" : "=v"(hx));
-                brdf_row_inputs<GEO>(x, lp, cm, nr, zsrc, a.z_dim, hx, v);
-#else
                 brdf_row_inputs<GEO>(x, lp, cm, nr, zsrc, a.z_dim, h, v);
-#endif
 #pragma unroll
                 for (int sidx = 0; sidx < 2; ++sidx) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) pl[sidx][c][j] = (__bf16)v[8 * sidx + j];
-                    mfma_operand_fence(pl[sidx][c]);
                 }
             }
         }
-#ifdef NFX_XP_CLOBBER_TOP     // round-6 experiment: nothing of this wave lives in v248 .. v255 across this point
-        asm volatile("" ::: "v248", "v249", "v250", "v251", "v252", "v253", "v254", "v255");
-#endif
         bf16x8 ha[8][CT], hb[8][CT];
         Acc<CT> accs[2];
         Pre pre;
@@ -942,9 +832,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) NFX_XP_CAP_ATTR void brdf_compact_
         NFX_LV3_TILE(5, 8, 0, ha, pl, NFX_LV3_EPI(4, hb, 0), NFX_LV3_BIAS(128 + 64));
         NFX_LV3_TILE(6, 8, 0, ha, pl, NFX_LV3_EPI(5, hb, 1), NFX_LV3_BIAS(128 + 96));
         NFX_LV3_TILE(7, 8, 0, ha, pl, NFX_LV3_EPI(6, hb, 2), NFX_LV3_BIAS(256));
-#ifdef NFX_XP_CLOBBER_TOP     // round-6 experiment: nothing of this wave lives in v248 .. v255 across this point
-        asm volatile("" ::: "v248", "v249", "v250", "v251", "v252", "v253", "v254", "v255");
-#endif
         NFX_LV3_TILE(8, 8, 0, hb, pl, NFX_LV3_EPI(7, hb, 3), NFX_LV3_BIAS(256 + 32));
         NFX_LV3_TILE(9, 8, 0, hb, pl, NFX_LV3_EPI(8, ha, 0), NFX_LV3_BIAS(256 + 64));
         NFX_LV3_TILE(10, 8, 0, hb, pl, NFX_LV3_EPI(9, ha, 1), NFX_LV3_BIAS(256 + 96));
@@ -960,15 +847,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) NFX_XP_CAP_ATTR void brdf_compact_
         if (h == 0) {
 #pragma unroll
             for (int c = 0; c < CT; ++c)
-#ifdef NFX_XP_NOSCRATCH      // (the libm log1pf keeps a constant pair live that the allocator spills; hardware exp / log: all CT / NW forms alike)
-                if (orow[c] >= 0) a.out[orow[c]] = fmaxf(accs[0].v[c][0], 0.0f) + __logf(1.0f + __expf(-fabsf(accs[0].v[c][0])));
-#else
                 if (orow[c] >= 0) a.out[orow[c]] = softplusf(accs[0].v[c][0]);   // brdf.py:65
-#endif
         }
-#ifdef NFX_XP_CLOBBER_TOP     // round-6 experiment: nothing of this wave lives in v248 .. v255 across this point
-        asm volatile("" ::: "v248", "v249", "v250", "v251", "v252", "v253", "v254", "v255");
-#endif
         head = ring_wrap(head + rows, kCap);
         cnt -= rows;
         if (cnt > 0) {
@@ -1048,9 +928,6 @@ extern "C" int nfx_launch_brdf_spec_v3(const float* xyz, const float* cam, const
     const int tiles = ct == 8 ? 2 : ct;
     if (n_lights > 1024 || tiles * 32 - 1 + n_lights > nfx::lv2::kRing) return -1;   // (launch_compact checks its own ring)
     nfx::lv2::Args a{xyz, lxyz, nullptr, cam, normal, z, z_dim, n, n_lights, (const char*)blob, spec};
-#ifdef NFX_EXPERIMENT_BUILD   // the per-row-geometry form with two waves per SIMD: NOT deterministic on MI355X (profiles/HISTORY.md section 2c), soak builds only
-    if (ct == 8 && !geo) return launch_compact<2, 0, 8>(a, max_blocks, st);
-#endif
     if (ct == 8) return geo ? launch_compact<2, 1, 8>(a, max_blocks, st) : launch_compact<2, 0, 4>(a, max_blocks, st);
     if (ct == 2) return geo ? launch_compact<2, 1, 4>(a, max_blocks, st) : launch_compact<2, 0, 4>(a, max_blocks, st);
     if (ct == 3) return geo ? launch_compact<3, 1, 4>(a, max_blocks, st) : launch_compact<3, 0, 4>(a, max_blocks, st);

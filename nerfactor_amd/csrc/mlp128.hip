@@ -232,7 +232,6 @@ __global__ __launch_bounds__(kNW * 64, 2) void brdf_spec_kernel(
         for (int s = 0; s < 2; ++s) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) bin[s][0][j] = (__bf16)v[8 * s + j];
-            mfma_operand_fence(bin[s][0]);
         }
         layer<2, 0, 4, kNL0, kNLH, true, kNW>(ws, tid, bias_lds, bin, bin, ha);
         mid_layers<kNL3>(ws, tid, bias_lds, ha, hb, bin);

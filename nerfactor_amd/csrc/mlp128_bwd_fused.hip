@@ -49,10 +49,7 @@ namespace bwd {
 namespace fused {
 
 constexpr int kNW = 4, kRows = kNW * 32;
-#ifndef NFX_FUSED_RING
-#define NFX_FUSED_RING 5
-#endif
-constexpr int kR = NFX_FUSED_RING, kD = kR - 1, kSlot = 8192;
+constexpr int kR = 5, kD = kR - 1, kSlot = 8192;
 constexpr int kFwdSub = 21;   // sub-chunks per tile: forward 0-20, dgrad through `out` 21-22, W3 23-26, W2 27-30, W1 31-34
 // PART 0 (layers 3 and out) stops behind dZ3: 23 sub-chunks per tile; PART 1 (layers 2, 1, 0) runs the whole chain: 35
 constexpr int sub_n(int part) { return part == 0 ? 23 : 35; }
@@ -242,8 +239,6 @@ __device__ __forceinline__ void relu_tile(const f32x16& acc, bf16x8& lo, bf16x8&
     if constexpr (BITS) bits = w;
     lo = __builtin_bit_cast(bf16x8, wl);
     hi = __builtin_bit_cast(bf16x8, wh);
-    mfma_operand_fence(lo);
-    mfma_operand_fence(hi);
 }
 // one forward layer of 4 tiles whose chunk is ONE sub-chunk each (K0 = its first sub-chunk)
 // `park` (optional): the tile's two output k-steps go to this lane's parked row in LDS as soon as they exist
@@ -301,8 +296,6 @@ __device__ __forceinline__ void relu_mask(const f32x16& acc, const bf16x8 (&hact
     }
     olo = __builtin_bit_cast(bf16x8, wl);
     ohi = __builtin_bit_cast(bf16x8, wh);
-    mfma_operand_fence(olo);
-    mfma_operand_fence(ohi);
 }
 // dgrad layer, one sub-chunk (8 fragments) per 32-feature tile: dH^T = W dZ^T, ReLU-masked by the activation
 template <int KSX, int NS, int K0, int MODE, bool HAVE>
@@ -339,10 +332,7 @@ __device__ __forceinline__ void store_rows(char* row, int lx, const bf16x8 (&v)[
 // Software-pipelined (round 5): the transposing reads of MFMA s + kWgradAhead are issued before MFMA s.  Round 4 read an
 // operand and used it at once — "ds_read_tr x2, s_waitcnt lgkmcnt(0), MFMA" 104 times a PART-1 tile, the LDS latency
 // exposed every time (142 full lgkmcnt drains per tile in the ISA, a quarter of the wave's time waiting on a counter).
-#ifndef NFX_FUSED_WGRAD_AHEAD
-#define NFX_FUSED_WGRAD_AHEAD 2
-#endif
-constexpr int kWgradAhead = NFX_FUSED_WGRAD_AHEAD;
+constexpr int kWgradAhead = 2;
 template <int NI, int A0, int NA, int NO>
 __device__ __forceinline__ void wgrad(const char* a, const int (&alo)[NO], const int (&ahi)[NO], const char* b, int blo, int bhi,
                                       f32x16 (&acc)[NA], float* bsum) {

@@ -42,23 +42,10 @@ constexpr int kPieceThreads = 256;                // a "piece" = 256 lanes x 16 
 // scheduling regions at every tile: that build is a different, 27 % slower kernel (131 k cycles per pass against 103 k).
 // In the PRODUCT schedule the same "operands never rewritten" experiment is worth 3.5 % (1518 against 1466 TFLOP/s),
 // and the moves that heal it cost more than they recover: -1.6 % (v_mov_b32 per pair), -1.0 % (eight v_mov_b64 per
-// tile); the light-visibility kernel -2.7 %, the density-gradient kernel -19 %.  The helpers stay as an opt-in
-// (-DNFX_OPERAND_FENCE) at every place an MFMA operand is converted, for whoever re-measures on another toolchain.
+// tile); the light-visibility kernel -2.7 %, the density-gradient kernel -19 %.  So no operand is re-written; the
+// opt-in fence (a `v_mov_b32 v, v` at every place an MFMA operand is converted), for whoever re-measures on another
+// toolchain, is in the history at commit 90ad7b3.
 // --------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned mfma_operand_dword(unsigned x) {
-#ifdef NFX_OPERAND_FENCE
-    asm("v_mov_b32 %0, %0" : "+v"(x));   // (not volatile: free to move between the instructions around it)
-#endif
-    return x;
-}
-__device__ __forceinline__ void mfma_operand_fence(bf16x8& v) {
-#ifdef NFX_OPERAND_FENCE
-    u32x4 w = __builtin_bit_cast(u32x4, v);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) w[q] = mfma_operand_dword(w[q]);
-    v = __builtin_bit_cast(bf16x8, w);
-#endif
-}
 
 template <int B, int E, typename F>
 __device__ __forceinline__ void static_for(F&& f) {
@@ -242,8 +229,6 @@ __device__ __forceinline__ void acc_to_b(const f32x16 (&acc)[CT], bf16x8 (&lo)[C
             lo[c][j] = (__bf16)v0;
             hi[c][j] = (__bf16)v1;
         }
-        mfma_operand_fence(lo[c]);
-        mfma_operand_fence(hi[c]);
     }
 }
 
@@ -353,7 +338,6 @@ __device__ __forceinline__ void posenc(const float (&x)[3], int h, int c,
     for (int s = 0; s < PeSlots<L>::kKS; ++s) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) out[s][c][j] = (__bf16)v[8 * s + j];
-        mfma_operand_fence(out[s][c]);
     }
 }
 

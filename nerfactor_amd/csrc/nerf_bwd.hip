@@ -60,8 +60,6 @@ __device__ __forceinline__ void dgrad_layer(WStream& ws, int tid, const bf16x8 (
             const bool on = MASK ? mask_bit(m, t, r) : true;
             dout[2 * t + (r >> 3)][0][r & 7] = (__bf16)(on ? acc[0][r] : 0.f);
         }
-        mfma_operand_fence(dout[2 * t][0]);
-        mfma_operand_fence(dout[2 * t + 1][0]);
         store_tile(fs, feat0 + 32 * t, h, dout[2 * t][0], dout[2 * t + 1][0]);
         __builtin_amdgcn_sched_barrier(0);
     });
@@ -181,10 +179,8 @@ __global__ __launch_bounds__(kNerfNW * 64, 1) void nerf_bwd_kernel(
 // L1 keeps in flight towards L2 — hence non-temporal activation stores (feat_store.hpp: the weights stay in L2) and
 // 8 waves per weight fetch.
 namespace nring {
-#ifndef NFX_NRING_D
-#define NFX_NRING_D 5   // fetch distance in chunks (experiments: 2 .. 5; 6 would exceed the 6-bit counter)
-#endif
-constexpr int kSeq = 152, kD = NFX_NRING_D, kR = kD + 1, kEpiStores = 8;
+// kD: fetch distance in chunks (measured 2 .. 5; 6 would exceed the 6-bit counter)
+constexpr int kSeq = 152, kD = 5, kR = kD + 1, kEpiStores = 8;
 // chunk i of a tile's sequence: first fragment in the train blob
 constexpr int off(int i) {
     if (i < 72) return nerf::chunk_frag_offset(i);                 // enc[0..7], bottleneck
@@ -314,8 +310,6 @@ __device__ __forceinline__ void dgrad_layer(const Ctx& cx, const bf16x8 (&dz)[KS
             const bool on = MASK ? mask_bit(m, t, r) : true;
             dout[2 * t + (r >> 3)][0][r & 7] = (__bf16)(on ? acc[0][r] : 0.f);
         }
-        mfma_operand_fence(dout[2 * t][0]);
-        mfma_operand_fence(dout[2 * t + 1][0]);
         store_tile(fs, feat0 + 32 * t, h, dout[2 * t][0], dout[2 * t + 1][0]);   // kEpiStores dword stores
         __builtin_amdgcn_sched_barrier(0);
     });

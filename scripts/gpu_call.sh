@@ -8,8 +8,7 @@
 #         bench-train-nerf-ab (nerf_bwd_rows) | wgrad-slabs-sweep (SLABS=...) | wgrad-rounds-ab | nerf-streams-ab | nerf-bwd-rows |
 #         prof-train-nerf | prof-nerf-bwd-rows (NBR_KIND=fitted|glorot) | geometry-ab (sigma_grad_rows) | sigma-variant-ab |
 #         soak-nerf-bwd | soak-sigma-v6 (SOAK_LAUNCHES=...)
-#   A / B stages (experiment builds: NFX_EXTRA_DEFS=... python -m nerfactor_amd.build --out nerfactor_amd/libnfx_xpX.so):
-#         fused-ab (AB_LIBS=...) | ring-ab (RING_LIBS=...) | generic-ab | splits-ab | generic-prof | generic-pmc
+#   runtime-shaped MLPs: generic-ab | splits-ab | generic-prof | generic-pmc
 set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
@@ -44,7 +43,6 @@ for w,v in d.items():
 PYEOF
               tail -3 $OUT/coarse_refine_probe.err ;;
     residual) timeout 600 python scripts/coarse_refine_residual.py > $OUT/coarse_refine_residual.json 2> $OUT/coarse_refine_residual.err; cat $OUT/coarse_refine_residual.json; tail -3 $OUT/coarse_refine_residual.err ;;
-    soak-libs) for lib in ${SOAK_LIBS:-libnfx_xp libnfx_xpN libnfx_xpS}; do echo "--- $lib"; NFX_LIB_PATH=$ROOT/nerfactor_amd/$lib.so REPS=${REPS:-30} timeout 500 python scripts/soak_8wave.py --geo0 > $OUT/soak_$lib.log 2>&1; grep -v "^  launch" $OUT/soak_$lib.log | tail -${SOAK_TAIL:-14}; done ;;
     time-refine) timeout 600 python scripts/time_refine.py > $OUT/time_refine.json 2> $OUT/time_refine.err; cat $OUT/time_refine.json; tail -3 $OUT/time_refine.err ;;
     bench-traffic) timeout 1200 python bench.py --gpus 1 --steps 10 --warmup 3 --measure-traffic --legs nerf,nerfactor_microfacet,olat > $OUT/bench_line_measured_traffic.json 2> $OUT/bench_traffic.err; cp bench_detail.json $OUT/bench_detail_measured_traffic.json; python -c "
 import json; d=json.load(open('$OUT/bench_detail_measured_traffic.json')); print('nerf', d['roofline']['traffic'], d['roofline']['traffic_source'][:60]); print('lvis', d['nerfactor']['nerfactor_microfacet']['roofline']['traffic'], d['nerfactor']['nerfactor_microfacet']['roofline']['traffic_source'][:40]); print('olat', d['olat']['roofline']['traffic'], d['olat']['roofline']['traffic_source'][:40])" ;;
@@ -85,7 +83,6 @@ for k,v in d.items():
         print(k[:70], {a: (round(b,4) if isinstance(b,float) and b<10 else int(b)) for a,b in v.items() if a in ('dispatches','mfma_util','SQ_WAIT_INST_ANY_frac_of_wave_cycles','SQ_WAIT_INST_LDS_frac_of_wave_cycles','SQ_LDS_BANK_CONFLICT','SQ_LDS_IDX_ACTIVE','hbm_read_bytes_corrected','hbm_write_bytes','SQ_BUSY_CYCLES','GRBM_GUI_ACTIVE','SQ_INSTS_LDS')})
 PYEOF
                ;;
-    soak-xp2) NFX_LIB_PATH=$ROOT/nerfactor_amd/libnfx_xp2.so timeout 600 python scripts/soak_8wave.py --geo0 > $OUT/soak_experiment_fastdiv.log 2>&1; tail -8 $OUT/soak_experiment_fastdiv.log ;;
     fitted)   timeout 600 python scripts/fitted_outliers.py > $OUT/fitted_outliers.json 2>&1; cat $OUT/fitted_outliers.json ;;
     pytest-k) timeout 1500 python -m pytest tests -m gpu -q ${PYTEST_FLAGS:-} -k "$PYTEST_K" > $OUT/pytest_gpu_k.log 2>&1; tail -${TAILN:-30} $OUT/pytest_gpu_k.log ;;
     bench-train) timeout 900 python bench.py --steps ${STEPS:-5} --warmup 2 --legs train --no-cpu-baseline > $OUT/bench_train.json 2> $OUT/bench_train.err; tail -c 2500 $OUT/bench_train.json; tail -3 $OUT/bench_train.err ;;
@@ -133,7 +130,6 @@ PYEOF
     nerf-bwd-rows) timeout 600 python scripts/nerf_bwd_rows.py > $OUT/nerf_bwd_rows.json 2> $OUT/nerf_bwd_rows.err; cat $OUT/nerf_bwd_rows.json; tail -3 $OUT/nerf_bwd_rows.err ;;
     bench-train-fp32) for m in nerfactor_microfacet nerfactor nerf shape; do for fm in "pairs" "pairs --graph" "native"; do timeout 300 python scripts/bench_train.py --model $m --precision fp32 --fp32-matrix $fm --steps 10 >> $OUT/bench_train_fp32.jsonl 2>> $OUT/bench_train_fp32.err; done; done; cat $OUT/bench_train_fp32.jsonl; tail -3 $OUT/bench_train_fp32.err ;;
     bench-train-unfused) NFX_WGRAD_FUSED=0 timeout 900 python bench.py --steps ${STEPS:-5} --warmup 2 --legs train --no-cpu-baseline --train-models nerfactor_microfacet > $OUT/bench_train_unfused.json 2> $OUT/bench_train_unfused.err; tail -c 1500 $OUT/bench_train_unfused.json ;;
-    soak-xp)  NFX_LIB_PATH=$ROOT/nerfactor_amd/libnfx_xp.so timeout 600 python scripts/soak_8wave.py --geo0 > $OUT/soak_experiment_build.log 2>&1; tail -16 $OUT/soak_experiment_build.log ;;
     generic)  timeout 600 python scripts/generic_rates.py > $OUT/generic_rates.json 2> $OUT/generic_rates.err; cat $OUT/generic_rates.json; tail -3 $OUT/generic_rates.err ;;
     generic-prof) (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/prof_generic -o g -- python $ROOT/scripts/generic_rates.py > $ROOT/$OUT/prof_generic_run.log 2>&1); find $OUT/prof_generic -name "*kernel_stats*" | head -1 | xargs -r head -12 ;;
     generic-pmc) for pass in "sq SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_WAIT_INST_LDS" "lds SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_LDS" "sq2 SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_MISC SQ_INST_CYCLES_SALU SQ_THREAD_CYCLES_VALU SQ_WAVES SQ_INSTS_MFMA"; do
@@ -177,20 +173,7 @@ for k,v in d.items():
         print(k[:64], {a: round(b/wc,4) for a,b in v.items() if a.startswith('SQ_') and a!='SQ_WAVE_CYCLES'}, int(wc))
 PYEOF
                done ;;
-    fused-ab) for lib in ${AB_LIBS:-libnfx libnfx_xp6 libnfx_xp7}; do NFX_LIB_PATH=$ROOT/nerfactor_amd/$lib.so timeout 300 python bench.py --legs train --train-models nerfactor_microfacet --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_train_$lib.json 2> $OUT/bench_train_$lib.err; python - <<PYEOF
-import json
-d=json.loads(open("$OUT/bench_train_$lib.json").read().strip().splitlines()[-1])
-t=d.get('train',d)
-print("$lib", json.dumps({k:v for k,v in (t.get('nerfactor_microfacet') or t).items() if not isinstance(v,(dict,list))})[:600])
-PYEOF
-               done ;;
     splits-ab) for sp in 64 128 256; do timeout 300 python scripts/generic_rates.py --only ${GENERIC_ONLY:-surface_128x4_lvis_fp32,nerf_enc_256x8_fp32,surface_128x4_lvis_fp32_native,surface_128x4_lvis} --option wgrad_splits=$sp > $OUT/generic_rates_splits$sp.json 2> $OUT/generic_rates_splits$sp.err; echo "splits $sp"; cat $OUT/generic_rates_splits$sp.json; tail -2 $OUT/generic_rates_splits$sp.err; done ;;
-    ring-ab) for lib in ${RING_LIBS:-libnfx libnfx_xpA libnfx_xpB}; do NFX_LIB_PATH=$ROOT/nerfactor_amd/$lib.so timeout 300 python scripts/generic_rates.py > $OUT/generic_rates_$lib.json 2> $OUT/generic_rates_$lib.err; echo $lib; python - <<PYEOF
-import json
-d=json.load(open("$OUT/generic_rates_$lib.json"))
-for k,v in d.items(): print('  %-34s fwd %7.3f ms %6.1f TF   bwd %7.3f ms %6.1f TF' % (k, v['fwd_ms'], v['fwd_tflops'], v['bwd_ms'], v['bwd_tflops']))
-PYEOF
-               tail -1 $OUT/generic_rates_$lib.err; done ;;
     step-trace) (cd /tmp && timeout 400 rocprofv3 --kernel-trace --output-format csv -d $ROOT/$OUT/step_trace -o t -- python $ROOT/bench.py --legs train --train-models ${TRACE_MODEL:-nerfactor_microfacet} --steps 3 --warmup 1 --no-cpu-baseline --no-hip-graph > $ROOT/$OUT/step_trace_run.log 2>&1); python scripts/step_trace.py $(find $OUT/step_trace -name "*kernel_trace.csv" | head -1) ${TRACE_MIN_US:-1000} > $OUT/step_trace_${TRACE_MODEL:-nerfactor_microfacet}.txt; tail -${TRACE_TAIL:-45} $OUT/step_trace_${TRACE_MODEL:-nerfactor_microfacet}.txt ;;
     *) echo "unknown stage $st" ;;
   esac

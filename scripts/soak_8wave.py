@@ -4,12 +4,8 @@ position of the differing elements modulo 64 / 16 (a lane-group pattern) and the
 
     resident128_kernel<2, 0, 8>   light visibility, the DEFAULT          (option lvis_variant 8 against 4)
     brdf_compact_kernel<2, 1, 8>  learned BRDF, closed-form angles, OPT-IN (brdf_variant 6, brdf_ct 8 against 4)
-    brdf_compact_kernel<2, 0, 8>  learned BRDF, per-row geometry — built only with -DNFX_EXPERIMENT_BUILD
-                                  (brdf_variant 5, brdf_ct 8 against 4); r03: failed bit identity on a fresh MI355X
 
-    python scripts/soak_8wave.py                       # the two kernels of the product library
-    NFX_LIB_PATH=.../libnfx_xp.so python scripts/soak_8wave.py --geo0    # + <2, 0, 8> from an experiment build:
-        NFX_EXTRA_DEFS=-DNFX_EXPERIMENT_BUILD python -m nerfactor_amd.build --out nerfactor_amd/libnfx_xp.so
+    python scripts/soak_8wave.py
 Environment: REPS (default 40), SIZES (default "333,200000")."""
 import json
 import os
@@ -93,7 +89,4 @@ for n in sizes:
     bargs = (dev(xyz, cuda), dev(cam, cuda), dev(normal, cuda), dev(z, cuda), dev(lxyz, cuda), bblob)
     soak('brdf_compact_kernel<2,1,8> (opt-in)', lambda: ops.brdf_spec_fwd(*bargs), {'brdf_variant': 6, 'brdf_ct': 4},
          {'brdf_variant': 6, 'brdf_ct': 8}, n)
-    if '--geo0' in sys.argv:
-        soak('brdf_compact_kernel<2,0,8> (experiment build)', lambda: ops.brdf_spec_fwd(*bargs),
-             {'brdf_variant': 5, 'brdf_ct': 4}, {'brdf_variant': 5, 'brdf_ct': 8}, n)
 print(json.dumps({'device': torch.cuda.get_device_name(0), 'lib': _capi.LIB_PATH, 'summary': summary}))

@@ -139,11 +139,11 @@ def test_nerf_backward_ring_model_catches_a_miscounted_wait():
     assert replay_nring(4, 6)[1] > 63
 
 
-def test_nerf_backward_ring_model_is_the_kernel_source():
-    """The constants restated above are the ones in nerf_bwd.hip (a changed kernel must change this model)."""
+def test_nerf_backward_ring_model_matches_the_kernel_constants():
+    """The constants restated above are the ones in nerf_bwd.hip (a changed kernel must change this model): the sequence
+    length 152, the fetch distance 5 (a constant, no -D can change it), kR = kD + 1 and kEpiStores = 8."""
     src = open(os.path.join(os.path.dirname(__file__), '..', 'nerfactor_amd', 'csrc', 'nerf_bwd.hip')).read()
-    assert re.search(r'kSeq = 152, kD = NFX_NRING_D, kR = kD \+ 1, kEpiStores = 8;', src)
-    assert '#define NFX_NRING_D 5' in src
+    assert re.search(r'kSeq = 152, kD = 5, kR = kD \+ 1, kEpiStores = 8;', src)
     assert ('const int used = i < 8 ? 4 : i < 40 ? 16 : i < 48 ? 20 : i < 72 ? 16 : i < 76 ? 18' in src
             and ': j < 4 ? 1 : j < 12 ? 8 : j < 20 ? 17 : 16;' in src)
     assert 'int n = kEpiStores * (i < 0 ? 0 : i < kD - 1 ? i : kD - 1);' in src
