@@ -1,10 +1,17 @@
 #!/usr/bin/env python
 """bench.py — rays/sec (+ PSNR vs the CPU oracle) of the NeRFactor per-ray rendering hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--legs nerf,nerfactor_microfacet,nerfactor]
-                    [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR]
+    python bench.py --full --gpus N --steps K --warmup W [--legs nerf,nerfactor_microfacet,nerfactor] [--no-cpu-baseline] ...
 
-BASELINE.json's metric is "rays/sec (64 samples/ray, 512 light dirs) + PSNR vs TF ref"; one run times, back to back,
+A plain run (no --full) does what the headline `value` needs and nothing else: it sets up leg `nerf`, warms it up, times its
+K steps and prints the line (the contract's keys, `config`, `roofline` from the HIP events of those steps).  It is the
+headline leg of a --full run without its CPU baseline, parity blocks and counter children: the same setup, the same timed
+steps, the same `value` and `ms_per_step`.  --dump-outputs writes the last timed step of EVERY leg, so a plain run with it
+also runs the other legs' setup, warm-up and timed steps, still without their CPU work.  Every other option belongs to a
+--full run and is refused without it.
+
+BASELINE.json's metric is "rays/sec (64 samples/ray, 512 light dirs) + PSNR vs TF ref"; a --full run times, back to back,
 
   * leg `nerf` (the headline `value`; BASELINE.json configs[1], SURVEY.md §8d "C2"): 800x800 view, 64 coarse + 128
     fine samples per ray, white background, perturb off, synthetic glorot weights (opaque variant), rays from the
@@ -31,9 +38,9 @@ rank r owns rays [r n/N, (r+1) n/N) of each view), so per-GPU work stays 640 000
 renders ONE view per step sharded the same way.  value = all rays of all ranks / max-over-ranks time.
 
 Prints ONE JSON line on rank 0.  `roofline` describes the dominant kernel of the headline leg (fused NeRF MLP,
-MFMA-bound: algorithmic FLOPs / HIP-event time of its launches on the launch stream); each NeRFactor leg carries
-its own `roofline` (light-visibility kernel) and at N == 1 every leg carries a `cpu_baseline` (torch-CPU fp32 port of
-the reference op sequence, bounded sample) whose output doubles as the PSNR / max-abs reference for the GPU frame.
+MFMA-bound: algorithmic FLOPs / HIP-event time of its launches on the launch stream); in a --full run each NeRFactor leg
+carries its own `roofline` (light-visibility kernel) and at N == 1 every leg carries a `cpu_baseline` (torch-CPU fp32 port
+of the reference op sequence, bounded sample) whose output doubles as the PSNR / max-abs reference for the GPU frame.
 """
 import argparse
 import json
@@ -258,7 +265,7 @@ def measure_traffic(legs, extra=()):
             env = dict(os.environ, NFX_BENCH_CHILD='1', TMPDIR='/tmp')
             for name, counter in (('fetch', 'FETCH_SIZE'), ('write', 'WRITE_SIZE')):
                 cmd = ['rocprofv3', '--kernel-trace', '--pmc', counter, '--output-format', 'csv', '-d', os.path.join(tmp, name),
-                       '-o', 'p', '--', sys.executable, os.path.join(ROOT, 'bench.py'), '--legs', legs, '--steps', '1',
+                       '-o', 'p', '--', sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--legs', legs, '--steps', '1',
                        '--warmup', '1', '--no-cpu-baseline', '--no-hip-graph'] + list(extra)
                 res = subprocess.run(cmd, cwd='/tmp', env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=240)
                 if res.returncode != 0:
@@ -1501,13 +1508,22 @@ def self_launch(args, argv):
 
 
 # ------------------------------------------------------------------------------------------------ main
+FULL_LEGS = 'nerf,nerfactor_microfacet,nerfactor,train,olat,relight,fp32_class,geometry'
+# options that change nothing but what a --full run adds, or the headline's configuration (argparse dests)
+FULL_ONLY = ('legs', 'train_models', 'cpu_budget', 'no_cpu_baseline', 'no_hip_graph', 'no_last_sample_refine', 'precision',
+             'measure_traffic', 'fp32_modes', 'force_group')
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--scaling', choices=('weak', 'strong'), default='weak')
-    ap.add_argument('--legs', default='nerf,nerfactor_microfacet,nerfactor,train,olat,relight,fp32_class,geometry')
+    ap.add_argument('--full', action='store_true',
+                    help="besides the headline leg's timed steps: its CPU baseline and parity blocks, the other legs (--legs) and "
+                         "every option below but --dump-outputs (a plain run refuses them)")
+    ap.add_argument('--legs', help="with --full: the legs to run (default: %s)" % FULL_LEGS)
     ap.add_argument('--train-models', default='nerfactor_microfacet,nerfactor,nerf')
     ap.add_argument('--cpu-budget', type=float, default=10., help="seconds of CPU work for the NeRF baseline sample")
     ap.add_argument('--no-cpu-baseline', action='store_true')
@@ -1530,6 +1546,15 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.full:
+        args.legs = args.legs or FULL_LEGS
+    else:
+        given = ['--' + k.replace('_', '-') for k in FULL_ONLY if getattr(args, k) != ap.get_default(k)]
+        if given:
+            ap.error("%s: only with --full (a plain run times the headline leg alone)" % ', '.join(given))
+        # the headline leg without the CPU port, the parity blocks and the counter children that --no-cpu-baseline leaves out;
+        # --dump-outputs writes the last timed step of every leg, so with it the other legs' timed steps run too
+        args.legs, args.no_cpu_baseline = FULL_LEGS if args.dump_outputs else 'nerf', True
     global MEASURE_TRAFFIC, DUMP
     MEASURE_TRAFFIC = args.measure_traffic
 

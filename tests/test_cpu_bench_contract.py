@@ -251,3 +251,15 @@ def test_steps_below_one_is_a_usage_error():
     res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'],
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert res.returncode == 2 and '--steps must be >= 1' in res.stderr
+
+
+@pytest.mark.parametrize('opts', [['--legs', 'nerf'], ['--train-models', 'nerf'], ['--cpu-budget', '1'], ['--no-cpu-baseline'],
+                                  ['--no-hip-graph'], ['--no-last-sample-refine'], ['--precision', 'fp32'], ['--measure-traffic'],
+                                  ['--fp32-modes'], ['--force-group']])
+def test_a_plain_run_refuses_the_options_of_a_full_run(opts, capsys):
+    """Without --full the bench times the headline leg alone: an option that only a --full run acts on is a usage error,
+    raised before any device is touched, never silently ignored."""
+    with pytest.raises(SystemExit) as e:
+        bench.main(['--steps', '1'] + opts)
+    assert e.value.code == 2
+    assert '%s: only with --full' % opts[0] in capsys.readouterr().err

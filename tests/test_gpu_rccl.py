@@ -85,7 +85,7 @@ def test_bench_launches_its_own_ranks(nfx_lib, cuda, tmp_path):
     bench.py re-executes itself as two ranks and rank 0 prints the one line with world_size 2.  WITH the CPU baselines and
     parity blocks that only rank 0 runs: none of them may contain a collective (round 6: the training legs' reference-step parity
     did — ten training steps of its own, whose all-reduce waited for ranks that were not there; it is one-process-only now)."""
-    res = _bench(['--gpus', '2', '--steps', '1', '--warmup', '0', '--legs', 'nerf,train,nerfactor_microfacet', '--train-models',
+    res = _bench(['--full', '--gpus', '2', '--steps', '1', '--warmup', '0', '--legs', 'nerf,train,nerfactor_microfacet', '--train-models',
                   'nerfactor_microfacet', '--cpu-budget', '1'], NFX_BENCH_REHEARSAL='1')
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith('{"metric"')]
@@ -101,7 +101,7 @@ def test_bench_launches_its_own_ranks(nfx_lib, cuda, tmp_path):
 def test_bench_force_group_runs_the_training_leg_on_rccl(nfx_lib, cuda):
     """--force-group: one rank, nccl group initialised, the line says `collective_backend: nccl` and the training leg's
     all-reduce went through RCCL (train.*.collective in the detail file)."""
-    res = _bench(['--steps', '1', '--warmup', '0', '--legs', 'train', '--train-models', 'nerfactor_microfacet', '--no-cpu-baseline',
+    res = _bench(['--full', '--steps', '1', '--warmup', '0', '--legs', 'train', '--train-models', 'nerfactor_microfacet', '--no-cpu-baseline',
                   '--force-group'])
     assert res.returncode == 0, res.stderr[-3000:]
     line = json.loads([l for l in res.stdout.splitlines() if l.startswith('{"metric"')][-1])
