@@ -69,7 +69,7 @@ NFX_API int nfx_last_error(char *buf, size_t len);
 /* Process-wide integer options: kernel-variant selectors kept for A/B measurements and the identity tests, and the
  * persistent-grid sizes.  The library reads NO environment variable; a host sets what it wants before the calls it
  * should affect (set / unset are atomic, but not ordered against calls in flight on other threads).  Keys:
- *   nerf_variant (7)  nerf_blocks (256)  m128_blocks (256)  lvis_variant (8)  brdf_variant (6)  brdf_ct (4)
+ *   nerf_variant (7)  nerf_fold (1)  nerf_blocks (256)  m128_blocks (256)  lvis_variant (8)  brdf_variant (6)  brdf_ct (4)
  *   nerf_bwd (1)  nerf_bwd_nw (8)  m128_bwd (1)  wgrad_lds / wgrad_slabs / wgrad_narrow (by row count)
  *   wgrad_fused (1)  wgrad_map (1)  wgrad_splits (256)
  * (defaults in parentheses; every variant of a selector computes the same function, most of them bit-identically —
@@ -144,6 +144,20 @@ NFX_API int nfx_gen_z(float near, float far, int n_samples, int64_t n_rays, int 
 NFX_API int nfx_nerf_mlp_fwd(const float *dev_rayo, const float *dev_rayd, const float *dev_z,
                      int64_t n_rays, int n_samples, const void *dev_blob, int prec,
                      float *dev_rgbs, void *stream);
+
+/* The same at NFX_PREC_BF16 with the network's linear bottleneck layer folded into rgb_out[0]
+ * (two linear maps in a row are one: W' = Wb W0a, b0' = bb W0a + b0), 70 tiles per 64 points
+ * instead of 78.  sigma (rgbs[..., 3]) is bit-identical to nfx_nerf_mlp_fwd; the rgb logits differ
+ * by the rounding of one bf16 layer (no further from the fp32 network than nfx_nerf_mlp_fwd's).
+ * dev_blob is the unchanged nfx_nerf_pack_weights blob; every call folds it into dev_workspace
+ * (nfx_nerf_fold_workspace_bytes(), 16-byte aligned, not overlapping the blob) first - a few
+ * microseconds, never cached, because blobs are re-packed in place while a network trains.
+ * nfx_nerf_fold_blob is that first step alone (the render blob of csrc/nerf_fold_layout.hpp).   */
+NFX_API size_t nfx_nerf_fold_workspace_bytes(void);
+NFX_API int nfx_nerf_fold_blob(const void *dev_blob, void *dev_workspace, size_t workspace_bytes, void *stream);
+NFX_API int nfx_nerf_mlp_fwd_folded(const float *dev_rayo, const float *dev_rayd, const float *dev_z,
+                            int64_t n_rays, int n_samples, const void *dev_blob, void *dev_workspace,
+                            size_t workspace_bytes, float *dev_rgbs, void *stream);
 
 /* Volumetric compositing, Model.accumulate_sigma + Model._accumulate
  * (nerf.py:184-254; util/math.py:67-68 safe_cumprod; util/img.py:76-95 alpha_blend).

@@ -283,7 +283,9 @@ class NerfMlp(torch.autograd.Function):
             _join_side_streams()      # (a backward pass that raised never reached its callback)
         ctx.save_for_backward(rayo, rayd, z)
         ctx.cfg = (train_blob_fn, prec, params)
-        return ops.nerf_mlp_fwd(rayo, rayd, z, fwd_blob, prec)
+        # unfolded: the backward re-computes this forward from the train blob, rgb_out[0]'s ReLU masks must come from the
+        # same arithmetic
+        return ops.nerf_mlp_fwd(rayo, rayd, z, fwd_blob, prec, fold=False)
 
     @staticmethod
     def backward(ctx, d_rgbs):

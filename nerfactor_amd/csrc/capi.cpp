@@ -11,6 +11,7 @@
 
 #include "../../include/nfx.h"
 #include "nerf_layout.hpp"
+#include "nerf_fold_layout.hpp"
 #include "pack.hpp"
 
 static thread_local char g_err[512] = "";
@@ -43,6 +44,11 @@ int nfx_launch_nerf_mlp_x3(const float*, const float*, const float*, long long, 
                            hipStream_t);
 int nfx_launch_nerf_mlp_bf16_v6(const float*, const float*, const float*, long long, int, const void*, float*, int,
                                 int, hipStream_t);
+int nfx_launch_nerf_fold(const void*, void*, hipStream_t);
+int nfx_launch_nerf_mlp_bf16_fold(const float*, const float*, const float*, long long, int, const void*, float*, int, int,
+                                  hipStream_t);
+int nfx_launch_nerf_mlp_bf16_v6_fold(const float*, const float*, const float*, long long, int, const void*, float*, int,
+                                     int, hipStream_t);
 int nfx_launch_l2_normalize3(const float*, float*, long long, float, hipStream_t);
 int nfx_launch_nonfinite(const float*, long long, int*, hipStream_t);
 int nfx_launch_gen_z(float, float, int, long long, int, const float*, float*, hipStream_t);
@@ -75,6 +81,9 @@ struct Option {
 };
 Option g_options[] = {
     {"nerf_variant", {0}, {0}},   // NeRF MLP forward: 7 (default) | 6 | 8 | 1 | 0 — all bit-identical
+    {"nerf_fold", {0}, {0}},      // 1 / unset: the HOST side (ops.nerf_mlp_fwd) renders bf16 through nfx_nerf_mlp_fwd_folded (bottleneck folded
+                                  //    into rgb_out[0]: same density bits, rgb logits within one bf16 layer's rounding); 0 = nfx_nerf_mlp_fwd.
+                                  //    The library only stores it.
     {"nerf_blocks", {0}, {0}},    // persistent grid of the NeRF kernels (default 256)
     {"m128_blocks", {0}, {0}},    // persistent grid of the width-128 kernels (default 256)
     {"lvis_variant", {0}, {0}},   // light visibility: 8 (default) | 2 | 3 | 4 | 0 — all bit-identical
@@ -295,6 +304,45 @@ int nfx_nerf_mlp_fwd(const float* rayo, const float* rayd, const float* z, int64
         return hip_result(nfx_launch_nerf_mlp_x3(rayo, rayd, z, n_pts, n_samples, blob, rgbs, blocks, (hipStream_t)stream),
                           "nerf_mlp_fwd(fp32 via 3 x bf16)");
     return fail(NFX_EINVAL, "nfx_nerf_mlp_fwd: bad prec %d", prec);
+}
+
+// ---- the bottleneck folded into rgb_out[0] (nerf_fold.hip, nerf_fold_layout.hpp)
+size_t nfx_nerf_fold_workspace_bytes(void) { return nfx::nerf::fold::kBlobBytes; }
+
+int nfx_nerf_fold_blob(const void* blob, void* workspace, size_t workspace_bytes, void* stream) {
+    REQUIRE(blob && workspace, "nfx_nerf_fold_blob: null pointer");
+    REQUIRE(workspace_bytes >= nfx_nerf_fold_workspace_bytes(), "nfx_nerf_fold_blob: workspace too small (%zu < %zu)",
+            workspace_bytes, nfx_nerf_fold_workspace_bytes());
+    if (!ALIGNED(blob, 16) || !ALIGNED(workspace, 16))
+        return fail(NFX_EALIGN, "nfx_nerf_fold_blob: blob and workspace must be 16-byte aligned");
+    const uintptr_t b = (uintptr_t)blob, w = (uintptr_t)workspace;
+    REQUIRE(b + nfx::nerf::kBlobBytes <= w || w + nfx_nerf_fold_workspace_bytes() <= b,
+            "nfx_nerf_fold_blob: the workspace overlaps the blob");
+    return hip_result(nfx_launch_nerf_fold(blob, workspace, (hipStream_t)stream), "nerf_fold_blob");
+}
+
+int nfx_nerf_mlp_fwd_folded(const float* rayo, const float* rayd, const float* z, int64_t n_rays, int n_samples,
+                            const void* blob, void* workspace, size_t workspace_bytes, float* rgbs, void* stream) {
+    REQUIRE(n_rays >= 0 && n_samples >= 1, "nfx_nerf_mlp_fwd_folded: bad shape (%lld rays, %d samples)",
+            (long long)n_rays, n_samples);
+    if (n_rays == 0) return NFX_OK;
+    REQUIRE(rayo && rayd && z && blob && rgbs, "nfx_nerf_mlp_fwd_folded: null pointer");
+    if (!ALIGNED(rgbs, 16)) return fail(NFX_EALIGN, "nfx_nerf_mlp_fwd_folded: rgbs must be 16-byte aligned");
+    // folded on every call, never cached: blobs are re-packed in place on the device while a network trains
+    const int rc = nfx_nerf_fold_blob(blob, workspace, workspace_bytes, stream);
+    if (rc) return rc;
+    const long long n_pts = (long long)n_rays * n_samples;
+    const int blocks = env_int("nerf_blocks", 256);
+    const int variant = env_int("nerf_variant", 7);   // as nfx_nerf_mlp_fwd; all bit-identical to each other
+    if (variant == 6 || variant == 7 || variant == 8)
+        return hip_result(nfx_launch_nerf_mlp_bf16_v6_fold(rayo, rayd, z, n_pts, n_samples, workspace, rgbs, blocks,
+                                                           variant == 8 ? 2 : variant == 7 ? 1 : 0, (hipStream_t)stream),
+                          "nerf_mlp_fwd_folded(bf16, v6-8)");
+    if (variant != 0 && variant != 1)
+        return fail(NFX_EINVAL, "nfx_nerf_mlp_fwd_folded: NFX_NERF_VARIANT %d is not built (0, 1, 6, 7, 8)", variant);
+    return hip_result(nfx_launch_nerf_mlp_bf16_fold(rayo, rayd, z, n_pts, n_samples, workspace, rgbs, variant, blocks,
+                                                    (hipStream_t)stream),
+                      "nerf_mlp_fwd_folded(bf16)");
 }
 
 int nfx_composite_fwd(const float* rgbs, const float* z, const float* rayd, const float* noise,

@@ -3,17 +3,22 @@
 // generation of nerf.py:162-164 / 175-177 and Embedder.__call__ (networks/embedder.py:46-47).
 #include "mlp_engine.hpp"
 #include "nerf_layout.hpp"
+#include "nerf_fold_layout.hpp"
 
 namespace nfx {
 
 // LDS: [2 weight slots][biases]
 constexpr int kNerfLdsBytes = 2 * kSlotBytes + nerf::kBiasFloats * 4;
 
-template <int CT, int NW>
-__global__ __launch_bounds__(NW * 64, NW / 4) void nerf_mlp_bf16_kernel(
+// FOLD: the blob is a RENDER blob (nerf_fold_layout.hpp, written by nerf_fold.hip): the linear bottleneck is folded into
+// rgb_out[0], its 8 tiles are not walked and the sigma tile and rgb_out[0] both read enc[7]'s output (70 chunks; the two
+// slots of this ring alternate whatever the chunk count).
+template <int CT, int NW, bool FOLD>
+__device__ __forceinline__ void nerf_mlp_bf16_body(
     const float* __restrict__ rayo, const float* __restrict__ rayd, const float* __restrict__ zbuf,
     long long n_pts, int n_samples, const char* __restrict__ blob, float4* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int kWBytes = FOLD ? nerf::fold::kWeightBytes : nerf::kWeightBytes;
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int h = lane >> 5, p = lane & 31;
@@ -22,12 +27,12 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void nerf_mlp_bf16_kernel(
 
     float* bias_lds = reinterpret_cast<float*>(smem + 2 * kSlotBytes);
     {
-        const float* bsrc = reinterpret_cast<const float*>(blob + nerf::kWeightBytes);
+        const float* bsrc = reinterpret_cast<const float*>(blob + kWBytes);
         for (int i = tid; i < nerf::kBiasFloats; i += kWgThreads) bias_lds[i] = bsrc[i];
     }
     WStream ws;
     ws.gbase = reinterpret_cast<const u32x4*>(blob);
-    ws.gend = reinterpret_cast<const u32x4*>(blob + nerf::kWeightBytes);
+    ws.gend = reinterpret_cast<const u32x4*>(blob + kWBytes);
     ws.gnext = ws.gbase;
     ws.ring = smem;
     stream_prologue<nerf::kNL0, NW>(ws, tid);  // also orders the bias copy before first use
@@ -64,8 +69,9 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void nerf_mlp_bf16_kernel(
         layer<16, 4, 8, kNL5, kNLH, true, NW>(ws, tid, bias_lds + kBiasL0 + 256 * 5, ha, pe, hb);
         layer<16, 0, 8, kNLH, kNLH, true, NW>(ws, tid, bias_lds + kBiasL0 + 256 * 6, hb, pe, ha);
         layer<16, 0, 8, kNLH, kNLH, true, NW>(ws, tid, bias_lds + kBiasL0 + 256 * 7, ha, pe, hb);
-        // bottleneck (nerf.py:68, no activation) — rows 0..255 of the fused [bottleneck | sigma_out]
-        layer<16, 0, 8, kNLH, kNLH, false, NW>(ws, tid, bias_lds + kBiasBott, hb, pe, ha);
+        // bottleneck (nerf.py:68, no activation) — rows 0..255 of the fused [bottleneck | sigma_out]; folded: not computed,
+        // rgb_out[0] below multiplies enc[7]'s output by Wb W0a instead
+        if constexpr (!FOLD) layer<16, 0, 8, kNLH, kNLH, false, NW>(ws, tid, bias_lds + kBiasBott, hb, pe, ha);
         // sigma_out (nerf.py:67) — row 256 of the fused matrix = row 0 of tile 8
         float sigma[CT];
         {
@@ -76,7 +82,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void nerf_mlp_bf16_kernel(
         }
         // rgb_out[0]: Dense(128, relu) on concat(bottleneck, posenc(view)) (nerf.py:280-281)
         bf16x8 r0[8][CT];
-        layer<16, 2, 4, kNLR0, kNLR1, true, NW>(ws, tid, bias_lds + kBiasRgb0, ha, pv, r0);
+        if constexpr (FOLD) layer<16, 2, 4, kNLR0, kNLR1, true, NW>(ws, tid, bias_lds + kBiasRgb0, hb, pv, r0);
+        else layer<16, 2, 4, kNLR0, kNLR1, true, NW>(ws, tid, bias_lds + kBiasRgb0, ha, pv, r0);
         // rgb_out[1]: Dense(3)
         {
             f32x16 acc[CT];
@@ -91,6 +98,21 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void nerf_mlp_bf16_kernel(
     }
 }
 
+template <int CT, int NW>
+__global__ __launch_bounds__(NW * 64, NW / 4) void nerf_mlp_bf16_kernel(
+    const float* __restrict__ rayo, const float* __restrict__ rayd, const float* __restrict__ zbuf,
+    long long n_pts, int n_samples, const char* __restrict__ blob, float4* __restrict__ out) {
+    nerf_mlp_bf16_body<CT, NW, false>(rayo, rayd, zbuf, n_pts, n_samples, blob, out);
+}
+
+namespace fold {
+template <int CT, int NW>
+__global__ __launch_bounds__(NW * 64, NW / 4) void nerf_mlp_bf16_kernel(
+    const float* __restrict__ rayo, const float* __restrict__ rayd, const float* __restrict__ zbuf,
+    long long n_pts, int n_samples, const char* __restrict__ blob, float4* __restrict__ out) {
+    nerf_mlp_bf16_body<CT, NW, true>(rayo, rayd, zbuf, n_pts, n_samples, blob, out);
+}
+}  // namespace fold
 
 // Variant 4: variant 1 (8 waves x 32 points, register-staged weights) with the six identical
 // 256->256 ReLU layers (enc[1..4], enc[6..7]) executed by ONE rolled two-layer loop body, to test
@@ -171,7 +193,7 @@ __global__ __launch_bounds__(512, 2) void nerf_mlp_bf16_rolled_kernel(
 
 }  // namespace nfx
 
-template <int CT, int NW>
+template <int CT, int NW, bool FOLD = false>
 static int launch_variant(const float* rayo, const float* rayd, const float* z, long long n_pts,
                           int n_samples, const void* blob, float* out, int max_blocks,
                           hipStream_t stream) {
@@ -179,7 +201,7 @@ static int launch_variant(const float* rayo, const float* rayd, const float* z, 
     const int tile_pts = NW * 32 * CT;
     const long long n_tiles = (n_pts + tile_pts - 1) / tile_pts;
     const int grid = (int)(n_tiles < max_blocks ? n_tiles : max_blocks);
-    auto kern = nerf_mlp_bf16_kernel<CT, NW>;
+    auto kern = FOLD ? fold::nerf_mlp_bf16_kernel<CT, NW> : nerf_mlp_bf16_kernel<CT, NW>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, kNerfLdsBytes);
     if (e != hipSuccess) return (int)e;
@@ -209,4 +231,14 @@ extern "C" int nfx_launch_nerf_mlp_bf16(const float* rayo, const float* rayd, co
     if (variant == 0)
         return launch_variant<2, 4>(rayo, rayd, z, n_pts, n_samples, blob, out, max_blocks, stream);
     return launch_variant<1, 8>(rayo, rayd, z, n_pts, n_samples, blob, out, max_blocks, stream);
+}
+
+// The same two variants over a RENDER blob (nerf_fold.hip): 70 tiles, the bottleneck folded into rgb_out[0].
+extern "C" int nfx_launch_nerf_mlp_bf16_fold(const float* rayo, const float* rayd, const float* z, long long n_pts,
+                                             int n_samples, const void* blob, float* out, int variant, int max_blocks,
+                                             hipStream_t stream) {
+    if (n_pts <= 0) return 0;
+    if (variant == 0)
+        return launch_variant<2, 4, true>(rayo, rayd, z, n_pts, n_samples, blob, out, max_blocks, stream);
+    return launch_variant<1, 8, true>(rayo, rayd, z, n_pts, n_samples, blob, out, max_blocks, stream);
 }

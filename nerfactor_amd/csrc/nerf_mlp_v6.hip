@@ -23,12 +23,18 @@
 #include "mlp_engine.hpp"
 #include "lds_dma.hpp"
 #include "nerf_layout.hpp"
-
+#include "nerf_fold_layout.hpp"
 
 // NFX_V6_SIGMA (nerf_sigma_v6.hip includes this file with it defined): the DENSITY-ONLY form of the same dataflow over the
 // GEOM blob (nerf_geom_layout.hpp: chunks 0..63 = the encoder exactly as here, chunk 64 = the sigma tile, chunk 65 = the
 // first reverse-sweep chunk, fetched and not multiplied: the weight sequence must be a multiple of the 6-slot ring) — the
 // tile / layer machinery below is shared, the kernel and the chunk count differ.
+//
+// FOLD (a template parameter of the tile machinery, false wherever it is not named): the same kernel over the RENDER blob
+// (nerf_fold_layout.hpp, written by nerf_fold.hip): the linear bottleneck is folded into rgb_out[0], its 8 tiles are gone and
+// the sigma tile and rgb_out[0] both read enc[7]'s output — 70 tiles.  70 is no multiple of the ring, so the chunk -> slot
+// map is no longer K % ring there (slot_of below; tests/test_cpu_nerf_fold.py proves the sequence in the happens-before
+// model of tests/test_cpu_ring_protocol.py).  The folded kernels are v6::fold::nerf_mlp_bf16_v6_kernel<AB, DMA>.
 #ifdef NFX_V6_SIGMA
 #define NFX_V6_NS v6s
 #else
@@ -45,16 +51,30 @@ constexpr int kNW = 4, kCT = 2;
 // DMA = 2 (variant 8): register-staged like 0, but chunk K+3 is fetched during tile K into one of TWO register sets and
 // written to its slot at the end of tile K+1: the global loads get two tile times to land instead of one, and the
 // compiler's counted vmcnt lets the newer set stay in flight across the store of the older one.
-template <int DMA> constexpr int ring_of = DMA == 1 ? 6 : 3;
+// Folded sequence (70 chunks): LDS-DMA keeps 6 slots, chunks 66..69 live in slots 1..4: any FIVE consecutive chunks of the
+// cyclic sequence sit in different slots, so the slot chunk K+3 is fetched into during tile K was last read in tile K-2 or
+// earlier.  Register-staged: a 4th slot for chunk 69 alone: any THREE consecutive chunks sit in different slots, as on the
+// 3-slot ring (chunk K+2 is stored at the end of tile K into a slot last read in tile K-1 or earlier).
+template <int DMA, bool FOLD = false> constexpr int ring_of = DMA == 1 ? 6 : FOLD ? 4 : 3;
+template <int DMA, bool FOLD> constexpr int slot_of(int k) {
+    if (!FOLD) return k % ring_of<DMA>;
+    return DMA == 1 ? (k < 66 ? k % 6 : k - 65) : (k == 69 ? 3 : k % 3);
+}
 constexpr int kDmaDist = 3;   // LDS-DMA fetch distance in tiles (4 measured the same; the 6-slot ring holds either)
 template <int DMA> constexpr int dist_of = DMA == 1 ? kDmaDist : DMA ? 3 : 2;
-template <int DMA> constexpr int lds_of = ring_of<DMA> * kSlotBytes + nerf::kBiasFloats * 4;
+template <int DMA, bool FOLD = false> constexpr int lds_of = ring_of<DMA, FOLD> * kSlotBytes + nerf::kBiasFloats * 4;
 #ifdef NFX_V6_SIGMA
 constexpr int kNChunks = 66;              // 64 encoder chunks + the sigma tile + one idle chunk = 6 x 11
 #else
 constexpr int kNChunks = nerf::kNChunks;  // 78
 #endif
 static_assert(kNChunks % 6 == 0, "the chunk sequence wraps on the 6-slot (and the 3-slot) ring");
+// the chunk sequence a kernel walks: the packed blob's, or the render blob's 70 chunks
+template <bool FOLD> constexpr int n_chunks = FOLD ? nerf::fold::kNChunks : kNChunks;
+template <bool FOLD> constexpr int seq_frags(int k) { return FOLD ? nerf::fold::chunk_frags(k) : nerf::chunk_frags(k); }
+template <bool FOLD> constexpr int seq_frag_offset(int k) {
+    return FOLD ? nerf::fold::chunk_frag_offset(k) : nerf::chunk_frag_offset(k);
+}
 
 constexpr int kPreA = 3;   // A fragments in flight ahead of their MFMAs (2 / 3 / 4 measured: 1373 / 1372 / 1363 TFLOP/s)
 
@@ -159,23 +179,25 @@ struct Ctx {
 // MFMA gaps of every tile, where a lone wave can hide five (MI355X_MICROARCH.md).  Only the fragments a tile really
 // multiplies are fetched (the chunks of layer 0, layer 5 and rgb_out[0] are padded to 8 / 24 fragments in the blob):
 // 298 pieces per pass instead of 318.
-constexpr int used_frags(int k) { return k < 8 ? 4 : k < 40 ? 16 : k < 48 ? 20 : k < 73 ? 16 : k < 77 ? 18 : 8; }
-constexpr int dma_pieces(int k) { return (used_frags(k) + kNW - 1) / kNW; }   // 1-KiB pieces per wave: 1 | 4 | 5 | 2
-template <int K>
+constexpr int used_frags(int k, bool fold = false) {
+    return k < 8 ? 4 : k < 40 ? 16 : k < 48 ? 20 : k < (fold ? 65 : 73) ? 16 : k < (fold ? 69 : 77) ? 18 : 8;
+}
+constexpr int dma_pieces(int k, bool fold = false) { return (used_frags(k, fold) + kNW - 1) / kNW; }   // 1-KiB pieces per wave: 1 | 4 | 5 | 2
+template <int K, bool FOLD>
 __device__ __forceinline__ void dma_chunk(const Ctx& cx) {
-    constexpr int n = dma_pieces(K);
+    constexpr int n = dma_pieces(K, FOLD);
     unsigned long long base = reinterpret_cast<unsigned long long>(cx.blob);
     unsigned lds = cx.smem_lds;
     asm volatile("" : "+s"(base), "+s"(lds));       // per tile: keeps the piece addresses out of the loop preheader
     const int piece0 = cx.wave * n;
-    const char* g = reinterpret_cast<const char*>(base) + (size_t)nerf::chunk_frag_offset(K) * kFragBytes + piece0 * 1024;
-    const unsigned l = lds + (K % 6) * kSlotBytes + piece0 * 1024;
+    const char* g = reinterpret_cast<const char*>(base) + (size_t)seq_frag_offset<FOLD>(K) * kFragBytes + piece0 * 1024;
+    const unsigned l = lds + slot_of<1, FOLD>(K) * kSlotBytes + piece0 * 1024;
     lds_dma_pieces<n>((cx.tid & 63) * 16, g, l);
 }
 // Tile K (global chunk index).  On entry `acc` holds the tile's bias and `pre` its first three A fragments; on exit
 // `acc_next` / `pre` hold the same for tile K+1 (bias from `next_bias`).  AB: timing-only ablation mask
 // (1 no weight staging, 2 no barrier, 4 no MFMA, 8 no A reads, 64 no bias reads).
-template <int K, int KS1, int KS2, int AB, int DMA, int KS1A, int KS2A, typename Epi>
+template <int K, int KS1, int KS2, int AB, int DMA, bool FOLD = false, int KS1A, int KS2A, typename Epi>
 __device__ __forceinline__ void tile(const Ctx& cx, Regs& rg, const float* next_bias, const bf16x8 (&b1)[KS1A][kCT],
                                      const bf16x8 (&b2)[KS2A][kCT], Acc& acc, Acc& acc_next, Pre& pre, Epi&& prev) {
     constexpr int KS = KS1 + KS2;
@@ -183,18 +205,17 @@ __device__ __forceinline__ void tile(const Ctx& cx, Regs& rg, const float* next_
     // (starting the previous tile's epilogue two k-steps into the tile, behind its first MFMAs, measured no gain on r01)
     constexpr int EOFF = 0;
     constexpr int SP = (PIECES < KS ? PIECES : KS - 1) + EOFF;  // k-step after which the previous tile's epilogue is complete
-    constexpr int R = ring_of<DMA>;
-    constexpr int K1 = (K + 1) % kNChunks, K2 = (K + dist_of<DMA>) % kNChunks;   // K2: the chunk fetched during this tile
-    constexpr int NL2 = nerf::chunk_frags(K2) / 4;
+    constexpr int K1 = (K + 1) % n_chunks<FOLD>, K2 = (K + dist_of<DMA>) % n_chunks<FOLD>;   // K2: the chunk fetched during this tile
+    constexpr int NL2 = seq_frags<FOLD>(K2) / 4;
     const int lane = cx.tid & 63;
-    const char* f0 = cx.smem + (K % R) * kSlotBytes + lane * 16;
+    const char* f0 = cx.smem + slot_of<DMA, FOLD>(K) * kSlotBytes + lane * 16;
     Stage<DMA ? 1 : NL2, kNW> st;
     if constexpr (DMA == 1 && !(AB & 1)) {
-        dma_chunk<K2>(cx);
+        dma_chunk<K2, FOLD>(cx);
     } else if constexpr (DMA == 2 && !(AB & 1)) {
         unsigned long long gb = reinterpret_cast<unsigned long long>(cx.blob);
         asm volatile("" : "+s"(gb));   // (an integer: a laundered generic pointer would turn the loads into flat_load)
-        const gu32x4* g = reinterpret_cast<const gu32x4*>(gb + (size_t)nerf::chunk_frag_offset(K2) * kFragBytes);
+        const gu32x4* g = reinterpret_cast<const gu32x4*>(gb + (size_t)seq_frag_offset<FOLD>(K2) * kFragBytes);
 #pragma unroll
         for (int k = 0; k < NL2; ++k) rg.r[K & 1][k] = g[k * kPieceThreads + cx.tid];
     } else if constexpr (!(AB & 1)) {
@@ -202,7 +223,7 @@ __device__ __forceinline__ void tile(const Ctx& cx, Regs& rg, const float* next_
         // and spilled (same cure as variant 2)
         unsigned long long gb = reinterpret_cast<unsigned long long>(cx.blob);
         asm volatile("" : "+s"(gb));
-        const gu32x4* g = reinterpret_cast<const gu32x4*>(gb + (size_t)nerf::chunk_frag_offset(K2) * kFragBytes);
+        const gu32x4* g = reinterpret_cast<const gu32x4*>(gb + (size_t)seq_frag_offset<FOLD>(K2) * kFragBytes);
 #pragma unroll
         for (int k = 0; k < NL2; ++k) st.r[k] = g[k * kPieceThreads + cx.tid];   // (kNW = 4: one piece group)
     }
@@ -240,19 +261,19 @@ __device__ __forceinline__ void tile(const Ctx& cx, Regs& rg, const float* next_
     if constexpr (DMA == 1 && !(AB & 1)) {
         // the chunk issued one tile ago must be complete before the barrier; this tile's pieces may stay in flight
         // (fetch distance 4: the chunk issued during the previous tile may stay in flight too)
-        constexpr int kInFlight = dma_pieces(K2) + (kDmaDist == 4 ? dma_pieces((K + 3) % kNChunks) : 0);
+        constexpr int kInFlight = dma_pieces(K2, FOLD) + (kDmaDist == 4 ? dma_pieces((K + 3) % n_chunks<FOLD>, FOLD) : 0);
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kInFlight) : "memory");
     } else if constexpr (DMA == 2 && !(AB & 1)) {
         // chunk K+2, fetched during tile K-1 into the other register set, to slot (K+2) % 3 = the slot tile K-1 read
-        constexpr int KP = (K + 2) % kNChunks, NLP = nerf::chunk_frags(KP) / 4;
-        u32x4* dst = reinterpret_cast<u32x4*>(cx.smem + (KP % R) * kSlotBytes);
+        constexpr int KP = (K + 2) % n_chunks<FOLD>, NLP = seq_frags<FOLD>(KP) / 4;
+        u32x4* dst = reinterpret_cast<u32x4*>(cx.smem + slot_of<DMA, FOLD>(KP) * kSlotBytes);
 #pragma unroll
         for (int k = 0; k < NLP; ++k) dst[k * kPieceThreads + cx.tid] = rg.r[(K + 1) & 1][k];
     } else if constexpr (!(AB & 1)) {
-        st.store(reinterpret_cast<u32x4*>(cx.smem + (K2 % R) * kSlotBytes), cx.tid);
+        st.store(reinterpret_cast<u32x4*>(cx.smem + slot_of<DMA, FOLD>(K2) * kSlotBytes), cx.tid);
     }
     if constexpr (!(AB & 8)) {
-        const char* f1 = cx.smem + (K1 % R) * kSlotBytes + lane * 16;
+        const char* f1 = cx.smem + slot_of<DMA, FOLD>(K1) * kSlotBytes + lane * 16;
 #pragma unroll
         for (int i = 0; i < kPreA; ++i) pre.a[i] = *reinterpret_cast<const bf16x8*>(f1 + i * kFragBytes);
     }
@@ -264,7 +285,7 @@ __device__ __forceinline__ void tile(const Ctx& cx, Regs& rg, const float* next_
 
 // A Dense layer of NT tiles starting at chunk K0, outputs to bout.  `prev0` = pending epilogue of tile K0-1;
 // `next_bias` = bias of the tile after this layer's last one.  On return the last tile's epilogue is pending.
-template <int K0, int KS1, int KS2, int NT, bool RELU, int AB, int DMA, int KS1A, int KS2A, int NTA, typename Epi0>
+template <int K0, int KS1, int KS2, int NT, bool RELU, int AB, int DMA, bool FOLD = false, int KS1A, int KS2A, int NTA, typename Epi0>
 __device__ __forceinline__ void layer(const Ctx& cx, Regs& rg, const float* bias, const float* next_bias,
                                       const bf16x8 (&b1)[KS1A][kCT], const bf16x8 (&b2)[KS2A][kCT],
                                       bf16x8 (&bout)[NTA][kCT], Acc (&accs)[2], Pre& pre, Epi0&& prev0) {
@@ -273,26 +294,26 @@ __device__ __forceinline__ void layer(const Ctx& cx, Regs& rg, const float* bias
         constexpr int K = K0 + t;
         const float* nb = t == NT - 1 ? next_bias : bias + 32 * (t + 1);
         if constexpr (t == 0) {
-            tile<K, KS1, KS2, AB, DMA>(cx, rg, nb, b1, b2, accs[K & 1], accs[(K + 1) & 1], pre, prev0);
+            tile<K, KS1, KS2, AB, DMA, FOLD>(cx, rg, nb, b1, b2, accs[K & 1], accs[(K + 1) & 1], pre, prev0);
         } else {
-            EpiB<RELU> e{accs[(K - 1) & 1], bout[2 * (t - 1)], bout[2 * (t - 1) + 1]};
-            tile<K, KS1, KS2, AB, DMA>(cx, rg, nb, b1, b2, accs[K & 1], accs[(K + 1) & 1], pre, e);
+                EpiB<RELU> e{accs[(K - 1) & 1], bout[2 * (t - 1)], bout[2 * (t - 1) + 1]};
+                tile<K, KS1, KS2, AB, DMA, FOLD>(cx, rg, nb, b1, b2, accs[K & 1], accs[(K + 1) & 1], pre, e);
         }
     });
 }
 
 #ifndef NFX_V6_SIGMA
-template <int AB, int DMA>
-__global__ __launch_bounds__(kNW * 64, 1) void nerf_mlp_bf16_v6_kernel(
+template <int AB, int DMA, bool FOLD>
+__device__ __forceinline__ void nerf_mlp_bf16_v6_body(
     const float* __restrict__ rayo, const float* __restrict__ rayd, const float* __restrict__ zbuf, long long n_pts,
     int n_samples, const char* __restrict__ blob, float4* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using namespace nerf;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, p = lane & 31;
     constexpr int kTilePts = kNW * 32 * kCT;
-    float* bias_lds = reinterpret_cast<float*>(smem + ring_of<DMA> * kSlotBytes);
+    float* bias_lds = reinterpret_cast<float*>(smem + ring_of<DMA, FOLD> * kSlotBytes);
     {
-        const float* bsrc = reinterpret_cast<const float*>(blob + kWeightBytes);
+        const float* bsrc = reinterpret_cast<const float*>(blob + (FOLD ? nerf::fold::kWeightBytes : nerf::kWeightBytes));
         for (int i = tid; i < kBiasFloats; i += kNW * 64) bias_lds[i] = bsrc[i];
     }
     typedef __attribute__((address_space(3))) char lds_char;
@@ -302,24 +323,24 @@ __global__ __launch_bounds__(kNW * 64, 1) void nerf_mlp_bf16_v6_kernel(
     Pre pre;
     Regs rg;
     if constexpr (DMA == 2) {   // chunk 2 plays "fetched during tile -1": register set 1, stored at the end of tile 0
-        const u32x4* g = reinterpret_cast<const u32x4*>(blob + (size_t)chunk_frag_offset(2) * kFragBytes);
+        const u32x4* g = reinterpret_cast<const u32x4*>(blob + (size_t)seq_frag_offset<FOLD>(2) * kFragBytes);
 #pragma unroll
-        for (int k = 0; k < chunk_frags(2) / 4; ++k) rg.r[1][k] = g[k * kPieceThreads + tid];
+        for (int k = 0; k < seq_frags<FOLD>(2) / 4; ++k) rg.r[1][k] = g[k * kPieceThreads + tid];
     }
     {   // chunks 0 and 1 -> slots 0 and 1
-        Stage<chunk_frags(0) / 4, kNW> s0;
-        Stage<chunk_frags(1) / 4, kNW> s1;
+        Stage<seq_frags<FOLD>(0) / 4, kNW> s0;
+        Stage<seq_frags<FOLD>(1) / 4, kNW> s1;
         s0.load(reinterpret_cast<const u32x4*>(blob), tid);
-        s1.load(reinterpret_cast<const u32x4*>(blob + (size_t)chunk_frag_offset(1) * kFragBytes), tid);
+        s1.load(reinterpret_cast<const u32x4*>(blob + (size_t)seq_frag_offset<FOLD>(1) * kFragBytes), tid);
         s0.store(reinterpret_cast<u32x4*>(smem), tid);
         s1.store(reinterpret_cast<u32x4*>(smem + kSlotBytes), tid);
         if constexpr (DMA == 1) {   // fetch distance 3: chunk 2 must be resident before the first tile as well
-            Stage<chunk_frags(2) / 4, kNW> s2;
-            s2.load(reinterpret_cast<const u32x4*>(blob + (size_t)chunk_frag_offset(2) * kFragBytes), tid);
+            Stage<seq_frags<FOLD>(2) / 4, kNW> s2;
+            s2.load(reinterpret_cast<const u32x4*>(blob + (size_t)seq_frag_offset<FOLD>(2) * kFragBytes), tid);
             s2.store(reinterpret_cast<u32x4*>(smem + 2 * kSlotBytes), tid);
             if constexpr (kDmaDist == 4) {
-                Stage<chunk_frags(3) / 4, kNW> s3;
-                s3.load(reinterpret_cast<const u32x4*>(blob + (size_t)chunk_frag_offset(3) * kFragBytes), tid);
+                Stage<seq_frags<FOLD>(3) / 4, kNW> s3;
+                s3.load(reinterpret_cast<const u32x4*>(blob + (size_t)seq_frag_offset<FOLD>(3) * kFragBytes), tid);
                 s3.store(reinterpret_cast<u32x4*>(smem + 3 * kSlotBytes), tid);
             }
         }
@@ -355,27 +376,41 @@ __global__ __launch_bounds__(kNW * 64, 1) void nerf_mlp_bf16_v6_kernel(
         };
         using T = std::true_type;
         using F = std::false_type;
-        // chunk index K: L0 0-7, L1-4 8-39, L5 40-47, L6-7 48-63, bottleneck 64-71, sigma 72, rgb0 73-76, rgb1 77;
-        // tile K accumulates in accs[K & 1]
-        layer<0, 4, 0, 8, true, AB, DMA>(cx, rg, bl, bl + 256 * 1, pe, pe, ha, accs, pre, EpiNone{});
-        layer<8, 16, 0, 8, true, AB, DMA>(cx, rg, bl + 256 * 1, bl + 256 * 2, ha, pe, hb, accs, pre, pend(T{}, accs[1], ha[14], ha[15]));
-        layer<16, 16, 0, 8, true, AB, DMA>(cx, rg, bl + 256 * 2, bl + 256 * 3, hb, pe, ha, accs, pre, pend(T{}, accs[1], hb[14], hb[15]));
-        layer<24, 16, 0, 8, true, AB, DMA>(cx, rg, bl + 256 * 3, bl + 256 * 4, ha, pe, hb, accs, pre, pend(T{}, accs[1], ha[14], ha[15]));
-        layer<32, 16, 0, 8, true, AB, DMA>(cx, rg, bl + 256 * 4, bl + 256 * 5, hb, pe, ha, accs, pre, pend(T{}, accs[1], hb[14], hb[15]));
-        layer<40, 16, 4, 8, true, AB, DMA>(cx, rg, bl + 256 * 5, bl + 256 * 6, ha, pe, hb, accs, pre, pend(T{}, accs[1], ha[14], ha[15]));
-        layer<48, 16, 0, 8, true, AB, DMA>(cx, rg, bl + 256 * 6, bl + 256 * 7, hb, pe, ha, accs, pre, pend(T{}, accs[1], hb[14], hb[15]));
-        layer<56, 16, 0, 8, true, AB, DMA>(cx, rg, bl + 256 * 7, bias_lds + kBiasBott, ha, pe, hb, accs, pre, pend(T{}, accs[1], ha[14], ha[15]));
+        // chunk index K: L0 0-7, L1-4 8-39, L5 40-47, L6-7 48-63, bottleneck 64-71, sigma 72, rgb0 73-76, rgb1 77
+        // (folded: sigma 64, rgb0 65-68, rgb1 69); tile K accumulates in accs[K & 1]
+        layer<0, 4, 0, 8, true, AB, DMA, FOLD>(cx, rg, bl, bl + 256 * 1, pe, pe, ha, accs, pre, EpiNone{});
+        layer<8, 16, 0, 8, true, AB, DMA, FOLD>(cx, rg, bl + 256 * 1, bl + 256 * 2, ha, pe, hb, accs, pre, pend(T{}, accs[1], ha[14], ha[15]));
+        layer<16, 16, 0, 8, true, AB, DMA, FOLD>(cx, rg, bl + 256 * 2, bl + 256 * 3, hb, pe, ha, accs, pre, pend(T{}, accs[1], hb[14], hb[15]));
+        layer<24, 16, 0, 8, true, AB, DMA, FOLD>(cx, rg, bl + 256 * 3, bl + 256 * 4, ha, pe, hb, accs, pre, pend(T{}, accs[1], ha[14], ha[15]));
+        layer<32, 16, 0, 8, true, AB, DMA, FOLD>(cx, rg, bl + 256 * 4, bl + 256 * 5, hb, pe, ha, accs, pre, pend(T{}, accs[1], hb[14], hb[15]));
+        layer<40, 16, 4, 8, true, AB, DMA, FOLD>(cx, rg, bl + 256 * 5, bl + 256 * 6, ha, pe, hb, accs, pre, pend(T{}, accs[1], ha[14], ha[15]));
+        layer<48, 16, 0, 8, true, AB, DMA, FOLD>(cx, rg, bl + 256 * 6, bl + 256 * 7, hb, pe, ha, accs, pre, pend(T{}, accs[1], hb[14], hb[15]));
+        if constexpr (FOLD) {
+        // enc[7] -> hb; next tile = sigma (bias row 256 of the fused [bottleneck | sigma_out] matrix)
+        layer<56, 16, 0, 8, true, AB, DMA, FOLD>(cx, rg, bl + 256 * 7, bias_lds + kBiasBott + 256, ha, pe, hb, accs, pre, pend(T{}, accs[1], ha[14], ha[15]));
+        // sigma tile (K = 64 -> accs[0]): the unfolded kernel's tile 72 on the same operands; pending: the last tile of enc[7]
+        // (accs[1] -> hb[14], hb[15], complete after k-step 8); next: folded rgb_out[0] tile 0
+        tile<64, 16, 0, AB, DMA, FOLD>(cx, rg, bias_lds + kBiasRgb0, hb, pe, accs[0], accs[1], pre, pend(T{}, accs[1], hb[14], hb[15]));
+        {   // folded rgb_out[0]: [enc[7] output, posenc(view)] -> 128 with W' = Wb W0a, b0' = bb W0a + b0 (nerf_fold.hip)
+            EpiSigma es{accs[0], sigma};
+            layer<65, 16, 2, 4, true, AB, DMA, FOLD>(cx, rg, bias_lds + kBiasRgb0, bias_lds + kBiasRgb1, hb, pv, r0, accs, pre, es);
+        }
+        // rgb_out[1] (K = 69 -> accs[1]); pending: last rgb_out[0] tile (K = 68 -> accs[0]); next: L0 tile 0
+        tile<69, 8, 0, AB, DMA, FOLD>(cx, rg, bl, r0, pe, accs[1], accs[0], pre, pend(T{}, accs[0], r0[6], r0[7]));
+        } else {
+        layer<56, 16, 0, 8, true, AB, DMA, FOLD>(cx, rg, bl + 256 * 7, bias_lds + kBiasBott, ha, pe, hb, accs, pre, pend(T{}, accs[1], ha[14], ha[15]));
         // bottleneck (no activation) hb -> ha; next tile = sigma (bias row 256 of the fused matrix)
-        layer<64, 16, 0, 8, false, AB, DMA>(cx, rg, bias_lds + kBiasBott, bias_lds + kBiasBott + 256, hb, pe, ha, accs, pre,
+        layer<64, 16, 0, 8, false, AB, DMA, FOLD>(cx, rg, bias_lds + kBiasBott, bias_lds + kBiasBott + 256, hb, pe, ha, accs, pre,
                                        pend(T{}, accs[1], hb[14], hb[15]));
         // sigma tile (K = 72 -> accs[0]); pending: last bottleneck tile (accs[1]); next: rgb_out[0] tile 0
-        tile<72, 16, 0, AB, DMA>(cx, rg, bias_lds + kBiasRgb0, hb, pe, accs[0], accs[1], pre, pend(F{}, accs[1], ha[14], ha[15]));
+        tile<72, 16, 0, AB, DMA, FOLD>(cx, rg, bias_lds + kBiasRgb0, hb, pe, accs[0], accs[1], pre, pend(F{}, accs[1], ha[14], ha[15]));
         {
             EpiSigma es{accs[0], sigma};
-            layer<73, 16, 2, 4, true, AB, DMA>(cx, rg, bias_lds + kBiasRgb0, bias_lds + kBiasRgb1, ha, pv, r0, accs, pre, es);
+            layer<73, 16, 2, 4, true, AB, DMA, FOLD>(cx, rg, bias_lds + kBiasRgb0, bias_lds + kBiasRgb1, ha, pv, r0, accs, pre, es);
         }
         // rgb_out[1] (K = 77 -> accs[1]); pending: last rgb_out[0] tile (K = 76 -> accs[0]); next: L0 tile 0
-        tile<77, 8, 0, AB, DMA>(cx, rg, bl, r0, pe, accs[1], accs[0], pre, pend(T{}, accs[0], r0[6], r0[7]));
+        tile<77, 8, 0, AB, DMA, FOLD>(cx, rg, bl, r0, pe, accs[1], accs[0], pre, pend(T{}, accs[0], r0[6], r0[7]));
+        }
         if (h == 0) {
 #pragma unroll
             for (int c = 0; c < kCT; ++c)
@@ -384,23 +419,40 @@ __global__ __launch_bounds__(kNW * 64, 1) void nerf_mlp_bf16_v6_kernel(
     }
 }
 
+
+template <int AB, int DMA>
+__global__ __launch_bounds__(kNW * 64, 1) void nerf_mlp_bf16_v6_kernel(
+    const float* __restrict__ rayo, const float* __restrict__ rayd, const float* __restrict__ zbuf, long long n_pts,
+    int n_samples, const char* __restrict__ blob, float4* __restrict__ out) {
+    nerf_mlp_bf16_v6_body<AB, DMA, false>(rayo, rayd, zbuf, n_pts, n_samples, blob, out);
+}
+
+namespace fold {   // over a render blob: 70 tiles
+template <int AB, int DMA>
+__global__ __launch_bounds__(kNW * 64, 1) void nerf_mlp_bf16_v6_kernel(
+    const float* __restrict__ rayo, const float* __restrict__ rayd, const float* __restrict__ zbuf, long long n_pts,
+    int n_samples, const char* __restrict__ blob, float4* __restrict__ out) {
+    nerf_mlp_bf16_v6_body<AB, DMA, true>(rayo, rayd, zbuf, n_pts, n_samples, blob, out);
+}
+}  // namespace fold
+
 #endif   // !NFX_V6_SIGMA
 }  // namespace NFX_V6_NS
 }  // namespace nfx
 
 #ifndef NFX_V6_SIGMA
-template <int AB, int DMA>
+template <int AB, int DMA, bool FOLD = false>
 static int launch_v6(const float* rayo, const float* rayd, const float* z, long long n_pts, int n_samples,
                      const void* blob, float* out, int max_blocks, hipStream_t stream) {
     using namespace nfx;
     const int tile_pts = v6::kNW * 32 * v6::kCT;
     const long long n_tiles = (n_pts + tile_pts - 1) / tile_pts;
     const int grid = (int)(n_tiles < max_blocks ? n_tiles : max_blocks);
-    auto kern = v6::nerf_mlp_bf16_v6_kernel<AB, DMA>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       v6::lds_of<DMA>);
+    auto kern = FOLD ? v6::fold::nerf_mlp_bf16_v6_kernel<AB, DMA> : v6::nerf_mlp_bf16_v6_kernel<AB, DMA>;
+    constexpr int lds = v6::lds_of<DMA, FOLD>;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(v6::kNW * 64), v6::lds_of<DMA>, stream, rayo, rayd, z, n_pts, n_samples,
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(v6::kNW * 64), lds, stream, rayo, rayd, z, n_pts, n_samples,
                        (const char*)blob, (float4*)out);
     return (int)hipGetLastError();
 }
@@ -412,5 +464,15 @@ extern "C" int nfx_launch_nerf_mlp_bf16_v6(const float* rayo, const float* rayd,
     if (dma_mode == 1) return launch_v6<0, 1>(rayo, rayd, z, n_pts, n_samples, blob, out, max_blocks, stream);   // variant 7
     if (dma_mode == 2) return launch_v6<0, 2>(rayo, rayd, z, n_pts, n_samples, blob, out, max_blocks, stream);   // variant 8
     return launch_v6<0, 0>(rayo, rayd, z, n_pts, n_samples, blob, out, max_blocks, stream);                      // variant 6
+}
+
+// The same three variants over a RENDER blob (nerf_fold.hip): 70 tiles, the bottleneck folded into rgb_out[0].
+extern "C" int nfx_launch_nerf_mlp_bf16_v6_fold(const float* rayo, const float* rayd, const float* z, long long n_pts,
+                                                int n_samples, const void* blob, float* out, int max_blocks, int dma_mode,
+                                                hipStream_t stream) {
+    if (n_pts <= 0) return 0;
+    if (dma_mode == 1) return launch_v6<0, 1, true>(rayo, rayd, z, n_pts, n_samples, blob, out, max_blocks, stream);
+    if (dma_mode == 2) return launch_v6<0, 2, true>(rayo, rayd, z, n_pts, n_samples, blob, out, max_blocks, stream);
+    return launch_v6<0, 0, true>(rayo, rayd, z, n_pts, n_samples, blob, out, max_blocks, stream);
 }
 #endif   // !NFX_V6_SIGMA

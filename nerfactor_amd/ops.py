@@ -289,8 +289,22 @@ def gen_z(near, far, n_samples, n_rays, lin_in_disp=False, u=None, device='cuda'
     return z
 
 
-def nerf_mlp_fwd(rayo, rayd, z, blob, prec='bf16'):
-    """rgbs[N,S,4] = NeRF MLP at rayo + rayd*z with view direction rayd (already normalised)."""
+def nerf_fold_blob(blob):
+    """The render blob of a packed bf16 NeRF blob (CUDA uint8): the bottleneck folded into rgb_out[0] on the device
+    (csrc/nerf_fold.hip).  nerf_mlp_fwd does this itself on every folded call; exposed for the tests."""
+    if not blob.is_cuda or blob.dtype != torch.uint8:
+        raise _capi.NfxError("blob must be a CUDA uint8 tensor")
+    ws = torch.empty(lib.nfx_nerf_fold_workspace_bytes(), dtype=torch.uint8, device=blob.device)
+    check(lib.nfx_nerf_fold_blob(_ptr(blob), _ptr(ws), ws.numel(), _stream()), 'nfx_nerf_fold_blob')
+    return ws
+
+
+def nerf_mlp_fwd(rayo, rayd, z, blob, prec='bf16', fold=None):
+    """rgbs[N,S,4] = NeRF MLP at rayo + rayd*z with view direction rayd (already normalised).
+
+    fold (bf16 only; no effect on 'fp32'): render with the network's linear bottleneck folded into rgb_out[0] — 70 tiles
+    instead of 78, the same density bits, rgb logits within one bf16 layer's rounding of the unfolded kernel's.  None =
+    the option `nerf_fold` (on unless set to 0).  Training passes False: its backward re-computes the unfolded forward."""
     rayo = _dev(rayo, 'rayo', (None, 3))
     n = rayo.shape[0]
     rayd = _dev(rayd, 'rayd', (n, 3))
@@ -299,6 +313,16 @@ def nerf_mlp_fwd(rayo, rayd, z, blob, prec='bf16'):
         raise _capi.NfxError("blob must be a CUDA uint8 tensor")
     s = z.shape[1]
     out = torch.empty((n, s, 4), dtype=torch.float32, device=z.device)
+    if fold is None:
+        fold = _capi.get_option('nerf_fold') != 0
+    if fold and _PREC[prec] == PREC_BF16:
+        # the render blob is re-made on every call (blobs are re-packed in place during training, a cache keyed on the
+        # address could go stale); the workspace comes from torch's caching allocator: no host synchronisation, safe
+        # under stream capture
+        ws = torch.empty(lib.nfx_nerf_fold_workspace_bytes(), dtype=torch.uint8, device=z.device)
+        check(lib.nfx_nerf_mlp_fwd_folded(_ptr(rayo), _ptr(rayd), _ptr(z), n, s, _ptr(blob), _ptr(ws), ws.numel(),
+                                          _ptr(out), _stream()), 'nfx_nerf_mlp_fwd_folded')
+        return out
     check(lib.nfx_nerf_mlp_fwd(_ptr(rayo), _ptr(rayd), _ptr(z), n, s, _ptr(blob), _PREC[prec],
                                _ptr(out), _stream()), 'nfx_nerf_mlp_fwd')
     return out
