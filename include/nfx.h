@@ -517,6 +517,13 @@ NFX_API int nfx_nerf_sigma_refine(const float *dev_rayo, const float *dev_rayd, 
                           int n_samples, const void *dev_geom_blob_fp32, const int *dev_list, const int *dev_count,
                           float *dev_rgbs, void *stream);
 
+/* The same for the LAST sample of every ray, the list implicit: rgbs[r, S - 1, 3] of rgbs[n_rays, S, 4] is overwritten with
+ * the fp32-class density at rayo[r] + rayd[r] z[r, S - 1], bit-identical to nfx_nerf_sigma_fwd(prec = NFX_PREC_FP32) there;
+ * nothing else is written.  That sample is composited with dist = 1e10 (nerf.py:186-191): its alpha is [sigma > 0], so the
+ * sign of its density is the one bit of a ray a bf16 kernel can get wrong by a whole pixel value.  One launch.           */
+NFX_API int nfx_nerf_sigma_refine_last(const float *dev_rayo, const float *dev_rayd, const float *dev_z, int64_t n_rays,
+                               int n_samples, const void *dev_geom_blob_fp32, float *dev_rgbs, void *stream);
+
 /* Occupancy grid of the density marches (csrc/occgrid.hip): R^3 cells over a box
  * (x_min, x_max, y_min, y_max, z_min, z_max; host floats, finite, min < max), one bit per cell — cell (i, j, k), i along x,
  * is bit c & 31 of word c >> 5 of dev_bits[ceil(R^3 / 32)], c = (i R + j) R + k; a point p with box_lo <= p <= box_hi lies in

@@ -100,6 +100,7 @@ SIGNATURES = {
     'nfx_shade_olat_fwd_rows': (_i, [_p, _p, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _f, _f, _i64, _i, _i, _p, _p, _p, _p]),
     'nfx_nerf_refine_select': (_i, [_p, _p, _p, _i64, _i, _f, _f, _f, _f, _i, _p, _p, _p]),
     'nfx_nerf_sigma_refine': (_i, [_p, _p, _p, _i64, _i, _p, _p, _p, _p, _p]),
+    'nfx_nerf_sigma_refine_last': (_i, [_p, _p, _p, _i64, _i, _p, _p, _p]),
     'nfx_nerf_sigma_fwd_list': (_i, [_p, _p, _p, _i64, _i, _p, _i, _p, _p, _p, _p]),
     'nfx_occgrid_workspace_bytes': (_sz, [_i64, _i]),
     'nfx_occgrid_select': (_i, [_p, _p, _p, _i64, _i, _p, _i, _p, _p, _p, _p, _sz, _p]),
@@ -150,7 +151,8 @@ def check(rc, what):
 
 # ------------------------------------------------------------------------------- options
 OPTION_KEYS = ('nerf_variant', 'nerf_fold', 'nerf_blocks', 'm128_blocks', 'lvis_variant', 'brdf_variant', 'brdf_ct', 'nerf_bwd',
-               'nerf_bwd_nw', 'm128_bwd', 'wgrad_lds', 'wgrad_slabs', 'wgrad_rounds', 'wgrad_narrow', 'wgrad_fused', 'lvis_verify', 'lvis_rows', 'brdf_bwd_rows', 'nerf_bwd_rows', 'sigma_grad_rows', 'sigma_variant')
+               'nerf_bwd_nw', 'm128_bwd', 'wgrad_lds', 'wgrad_slabs', 'wgrad_rounds', 'wgrad_narrow', 'wgrad_fused', 'lvis_verify', 'lvis_rows', 'brdf_bwd_rows', 'nerf_bwd_rows', 'sigma_grad_rows', 'sigma_variant',
+               'sigma_x3_variant')
 
 
 def set_option(key, value):

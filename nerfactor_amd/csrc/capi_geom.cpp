@@ -44,6 +44,8 @@ int nfx_launch_nerf_sigma_v6_list(const float*, const float*, const float*, long
                                   const int*, int, hipStream_t);   // nerf_sigma_v6.hip
 int nfx_launch_nerf_sigma_x3_list_flat(const float*, const float*, const float*, long long, int, const void*, float*,
                                        const int*, const int*, int, hipStream_t);
+int nfx_launch_nerf_sigma_x3_last(const float*, const float*, const float*, long long, int, const void*, float*, int,
+                                  hipStream_t);
 size_t nfx_occgrid_list_bytes(long long n_pts);   // occgrid.hip
 int nfx_launch_occgrid_select(const float*, const float*, const float*, long long, int, const uint32_t*, int, const float*,
                               const float*, float*, void*, hipStream_t);
@@ -197,6 +199,17 @@ int nfx_nerf_sigma_refine(const float* rayo, const float* rayd, const float* z, 
     return nfx_hip_result(nfx_launch_nerf_sigma_x3_list(rayo, rayd, z, (long long)n_rays * n_samples, n_samples, blob, rgbs,
                                                         list, count, nfx_option_int("nerf_blocks", 256),
                                                         (hipStream_t)stream), "nerf_sigma_refine");
+}
+
+int nfx_nerf_sigma_refine_last(const float* rayo, const float* rayd, const float* z, int64_t n_rays, int n_samples,
+                               const void* blob, float* rgbs, void* stream) {
+    REQUIRE(n_rays >= 0 && n_samples >= 1, "nfx_nerf_sigma_refine_last: bad shape");
+    if (n_rays == 0) return NFX_OK;
+    REQUIRE(rayo && rayd && z && blob && rgbs, "nfx_nerf_sigma_refine_last: null pointer");
+    if (!ALIGNED(blob, 16)) return nfx_fail(NFX_EALIGN, "nfx_nerf_sigma_refine_last: blob must be 16-byte aligned");
+    return nfx_hip_result(nfx_launch_nerf_sigma_x3_last(rayo, rayd, z, (long long)n_rays, n_samples, blob, rgbs,
+                                                        nfx_option_int("nerf_blocks", 256), (hipStream_t)stream),
+                          "nerf_sigma_refine_last");
 }
 
 int nfx_nerf_sigma_grad(const float* rayo, const float* rayd, const float* z, int64_t n_rays, int n_samples,

@@ -11,6 +11,10 @@
 #include "mlp_x3.hpp"
 #include "nerf_geom_layout.hpp"
 
+extern "C" int nfx_option_int(const char* name, int dflt);
+extern "C" int nfx_launch_nerf_sigma_x3_pipe(const float*, const float*, const float*, long long, int, const void*, float*,
+                                             const int*, const int*, int, int, int, hipStream_t);   // nerf_sigma_x3_pipe.hip
+
 namespace nfx {
 namespace geo3 {
 
@@ -70,7 +74,7 @@ template <bool GRAD>
 __global__ __launch_bounds__(kNW * 64, 1) void nerf_sigma_x3_kernel(
     const float* __restrict__ rayo, const float* __restrict__ rayd, const float* __restrict__ zbuf, long long n_pts,
     int n_samples, const char* __restrict__ blob, float* __restrict__ out, const int* __restrict__ list,
-    const int* __restrict__ count, int list_stride) {
+    const int* __restrict__ count, int list_stride, int last_sample) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using namespace nerf;
     // LIST mode (round 6): the points are the flat sample indices list[0 .. *count) (both in device memory: the number of
@@ -78,6 +82,7 @@ __global__ __launch_bounds__(kNW * 64, 1) void nerf_sigma_x3_kernel(
     // list_stride = 4: the sigma channel of rgbs[N, S, 4] (the selective coarse refinement of the bf16 render); 1: a flat
     // [N, S] (nfx_nerf_sigma_fwd_list, the occupancy-grid march); GRAD (nfx_nerf_sigma_grad_rows: the
     // samples with a positive density): (normal, sigma) of point i to row i of out[n][4].  A workgroup with no tile leaves at once.
+    // LAST-SAMPLE mode (density only): point i is the last sample of ray i, flat index (i + 1) S - 1, stored like a listed one.
     if (list != nullptr) {
         n_pts = *count;
         if ((long long)blockIdx.x * kRows >= n_pts) return;
@@ -104,6 +109,7 @@ __global__ __launch_bounds__(kNW * 64, 1) void nerf_sigma_x3_kernel(
         const bool valid = row < n_pts;
         long long mm = valid ? row : n_pts - 1;
         if (list != nullptr) mm = list[mm];
+        else if (!GRAD && last_sample) mm = (mm + 1) * n_samples - 1;
         float x[3];
         {
             const long long ray = mm / n_samples;
@@ -132,7 +138,7 @@ __global__ __launch_bounds__(kNW * 64, 1) void nerf_sigma_x3_kernel(
         }
         if constexpr (!GRAD) {
             if (valid && h == 0) {
-                if (list != nullptr) out[list_stride * (mm + 1) - 1] = sigma;
+                if (list != nullptr || last_sample) out[list_stride * (mm + 1) - 1] = sigma;
                 else out[row] = sigma;
             }
         } else {
@@ -190,15 +196,19 @@ __global__ __launch_bounds__(kNW * 64, 1) void nerf_sigma_x3_kernel(
 template <bool GRAD>
 static int launch(const float* rayo, const float* rayd, const float* z, long long n_pts, int n_samples,
                   const void* blob, float* out, int max_blocks, hipStream_t st, const int* list = nullptr,
-                  const int* count = nullptr, int list_stride = 4) {
+                  const int* count = nullptr, int list_stride = 4, int last_sample = 0) {
     if (n_pts <= 0) return 0;
+    // density only: the pipelined kernel (nerf_sigma_x3_pipe.hip) unless option sigma_x3_variant = 0; bit-identical
+    if (!GRAD && nfx_option_int("sigma_x3_variant", 1) != 0)
+        return nfx_launch_nerf_sigma_x3_pipe(rayo, rayd, z, n_pts, n_samples, blob, out, list, count, list_stride, last_sample,
+                                             max_blocks, st);
     const long long tiles = (n_pts + kRows - 1) / kRows;
     const int grid = (int)(tiles < max_blocks ? tiles : max_blocks);
     auto k = nerf_sigma_x3_kernel<GRAD>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(k, dim3(grid), dim3(kNW * 64), kLds, st, rayo, rayd, z, n_pts, n_samples, (const char*)blob, out,
-                       list, count, list_stride);
+                       list, count, list_stride, last_sample);
     return (int)hipGetLastError();
 }
 
@@ -231,4 +241,9 @@ extern "C" int nfx_launch_nerf_sigma_x3_list_flat(const float* rayo, const float
                                                   int n_samples, const void* blob, float* out, const int* list,
                                                   const int* count, int max_blocks, hipStream_t st) {
     return nfx::geo3::launch<false>(rayo, rayd, z, n_pts, n_samples, blob, out, max_blocks, st, list, count, 1);
+}
+// density of every ray's last sample, stored at the sigma channel of rgbs[n_rays, S, 4] (nfx_nerf_sigma_refine_last)
+extern "C" int nfx_launch_nerf_sigma_x3_last(const float* rayo, const float* rayd, const float* z, long long n_rays,
+                                             int n_samples, const void* blob, float* rgbs, int max_blocks, hipStream_t st) {
+    return nfx::geo3::launch<false>(rayo, rayd, z, n_rays, n_samples, blob, rgbs, max_blocks, st, nullptr, nullptr, 4, 1);
 }

@@ -972,14 +972,18 @@ def nerf_sigma_fwd(rayo, rayd, z, blob, prec='bf16'):
 
 def nerf_refine_last_sample(rayo, rayd, z, rgbs, geom_blob_fp32):
     """Overwrites the density of every ray's LAST sample in rgbs[N,S,4] (in place) with the fp32-class density kernel's
-    value (nerf_geom_x3.hip through nfx_nerf_sigma_fwd, NFX_PREC_FP32).  That sample gets dist = 1e10 when compositing
+    value (nfx_nerf_sigma_refine_last: one launch, the kernel reads z[:, -1] and writes rgbs[:, -1, 3] itself; the bits of
+    nerf_sigma_fwd(..., 'fp32') there).  That sample gets dist = 1e10 when compositing
     (nerf.py:186-191): alpha_last = [sigma_last > 0] exactly, so its SIGN is the only bit of the ray that a bf16 kernel
     can get wrong by a whole pixel value; 1 / S of the points at ~3x the cost."""
     n, s = z.shape
     if n == 0 or s < 2:
         return rgbs
-    sig = nerf_sigma_fwd(rayo, rayd, z[:, -1:].contiguous(), geom_blob_fp32, 'fp32')
-    rgbs[:, -1, 3] = sig[:, 0]
+    if not (isinstance(rgbs, torch.Tensor) and rgbs.is_contiguous()):
+        raise _capi.NfxError("nerf_refine_last_sample: rgbs is updated in place and must be contiguous")
+    rayo, rayd, z, n, s = _ray_args(rayo, rayd, z, geom_blob_fp32)
+    check(lib.nfx_nerf_sigma_refine_last(_ptr(rayo), _ptr(rayd), _ptr(z), n, s, _ptr(geom_blob_fp32),
+                                         _ptr(_dev(rgbs, 'rgbs', (n, s, 4))), _stream()), 'nfx_nerf_sigma_refine_last')
     return rgbs
 
 
