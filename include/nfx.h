@@ -634,6 +634,29 @@ NFX_API int nfx_embed(const float *dev_x, const float *dev_dir, const float *dev
 NFX_API int nfx_selftest_tr16(const float *dev_h, const float *dev_z, float *dev_d, int mode, void *stream);
 NFX_API int nfx_selftest_sincos(const float *dev_in, int64_t n, int which, float *dev_out, void *stream);
 
+/* The batched weight-gradient GEMMs of the tuned backward passes (csrc/train.hip) on operands of the caller's, exactly as
+ * nfx_nerf_mlp_bwd / nfx_mlp128_bwd (option wgrad_fused = 0) / nfx_brdf_rows_bwd launch them: no new kernel, nothing
+ * allocated.  Call i: dev_dw[i][k_in[i], n_out[i]] += X_i^T Z_i and, dev_db[i] != NULL, dev_db[i][n_out[i]] += column sums
+ * of Z_i, over rows [0, rows) — or [0, *dev_count) with dev_count != NULL, a number only the device knows (0 <= *dev_count
+ * <= rows; rows is then the capacity the plan and the workspace are sized for).  dev_xt[i] / dev_zt[i]: bf16,
+ * FEATURE-PAIR-major [ceil(F / 2)][ld][2] (csrc/feat_store.hpp), F = k_in[i] / n_out[i].  What the producers guarantee and
+ * the kernels rely on: rows [rows, ld) and, F odd, the odd half of the last pair are never read as numbers (they may hold
+ * anything); with dev_count the rows [*dev_count, round16(*dev_count)) hold zeros in dev_zt and finite values in dev_xt.
+ * Two calls may share an operand and may write disjoint ranges of one dW (the skip rows of the networks).  fp32 sums in
+ * a fixed order (bit-reproducible).  NFX_EINVAL, before anything is launched or written: n_calls outside 1 .. 16, rows not a
+ * multiple of 16, ld < rows or ld % 4 != 0, a workspace under nfx_selftest_wgrad_partial_bytes, a null operand, dev_count
+ * when the plan under the current options (wgrad_lds, wgrad_narrow) is not the wide LDS form.  NFX_EALIGN: dev_xt / dev_zt /
+ * dev_partial not 16-byte, dev_dw / dev_db / dev_count not 4-byte aligned.
+ * nfx_selftest_wgrad_plan (host only, no GPU work): how such a batch is cut under the current options (wgrad_lds,
+ * wgrad_slabs, wgrad_rounds, wgrad_narrow) — *use_lds: LDS-staged kernels (else one wave per 128 x 128 block straight from
+ * global memory), *wide: the 256 x 256 block form of them, n_slabs row slabs of `slab` rows. */
+NFX_API int nfx_selftest_wgrad_plan(int n_calls, const int *k_in, const int *n_out, int64_t rows, int *use_lds, int *wide,
+                                    int64_t *slab, int *n_slabs);
+NFX_API size_t nfx_selftest_wgrad_partial_bytes(int n_calls, const int *k_in, const int *n_out, int64_t rows);
+NFX_API int nfx_selftest_wgrad_batch(int n_calls, const void *const *dev_xt, const void *const *dev_zt, const int *k_in,
+                                     const int *n_out, float *const *dev_dw, float *const *dev_db, int64_t ld, int64_t rows,
+                                     const int32_t *dev_count, void *dev_partial, size_t partial_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,6 +113,9 @@ SIGNATURES = {
     'nfx_selftest_mfma_bf16': (_i, [_p, _p, _p, _p]),
     'nfx_selftest_sincos': (_i, [_p, _i64, _i, _p, _p]),
     'nfx_selftest_tr16': (_i, [_p, _p, _p, _i, _p]),
+    'nfx_selftest_wgrad_plan': (_i, [_i, _p, _p, _i64, _p, _p, _p, _p]),
+    'nfx_selftest_wgrad_partial_bytes': (_sz, [_i, _p, _p, _i64]),
+    'nfx_selftest_wgrad_batch': (_i, [_i, _pp, _pp, _p, _p, _pp, _pp, _i64, _i64, _p, _p, _sz, _p]),
     'nfx_mlp_generic_packed_bytes': (_sz, [_i, _i, _p, _p, _i]),
     'nfx_mlp_generic_pack': (_i, [_pp, _pp, _i, _i, _p, _p, _i, _p, _sz]),
     'nfx_mlp_generic_fwd': (_i, [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _i, _p, _i, _i, _p]),

@@ -683,4 +683,74 @@ int nfx_amsgrad_step_dev(float* p, const float* g, float* m, float* v, float* vh
     return nfx_hip_result(nfx_launch_amsgrad_dev(p, g, m, v, vhat, n, dev_lr_t, beta1, beta2, eps, (hipStream_t)stream),
                           "amsgrad_step_dev");
 }
+
+// ---------------------------------------------------------------- self-test door to the weight-gradient batch (train.hip)
+void nfx_wgrad_plan_of(const nfx_wgrad_call*, int, long long, int*, long long*, int*);
+int nfx_wgrad_max_calls(void);
+
+// the dims of a table as a call table without pointers (what the plan and the workspace size depend on)
+static int selftest_wgrad_table(const char* who, int n_calls, const int* k_in, const int* n_out, int64_t rows,
+                                std::vector<nfx_wgrad_call>* calls) {
+    REQUIRE(n_calls >= 1 && n_calls <= nfx_wgrad_max_calls(), "%s: 1 .. %d calls (got %d)", who, nfx_wgrad_max_calls(), n_calls);
+    REQUIRE(k_in && n_out, "%s: null dimension table", who);
+    REQUIRE(rows >= 0 && rows % 16 == 0, "%s: rows (%lld) must be a non-negative multiple of 16", who, (long long)rows);
+    calls->resize(n_calls);
+    for (int i = 0; i < n_calls; ++i) {
+        REQUIRE(k_in[i] >= 1 && n_out[i] >= 1, "%s: call %d: k_in and n_out must be >= 1", who, i);
+        (*calls)[i] = nfx_wgrad_call{nullptr, nullptr, k_in[i], n_out[i], nullptr, nullptr};
+    }
+    return NFX_OK;
+}
+
+int nfx_selftest_wgrad_plan(int n_calls, const int* k_in, const int* n_out, int64_t rows, int* use_lds, int* wide,
+                            int64_t* slab, int* n_slabs) {
+    std::vector<nfx_wgrad_call> calls;
+    if (int rc = selftest_wgrad_table("nfx_selftest_wgrad_plan", n_calls, k_in, n_out, rows, &calls)) return rc;
+    REQUIRE(rows > 0, "nfx_selftest_wgrad_plan: a batch without rows has no plan");
+    REQUIRE(use_lds && wide && slab && n_slabs, "nfx_selftest_wgrad_plan: null output");
+    int form;
+    long long sl;
+    nfx_wgrad_plan_of(calls.data(), n_calls, rows, &form, &sl, n_slabs);
+    *use_lds = form != 0;
+    *wide = form == 2;
+    *slab = sl;
+    return NFX_OK;
+}
+
+size_t nfx_selftest_wgrad_partial_bytes(int n_calls, const int* k_in, const int* n_out, int64_t rows) {
+    std::vector<nfx_wgrad_call> calls;
+    if (selftest_wgrad_table("nfx_selftest_wgrad_partial_bytes", n_calls, k_in, n_out, rows, &calls)) return 0;
+    return nfx_wgrad_partial_bytes(calls.data(), n_calls, rows);
+}
+
+int nfx_selftest_wgrad_batch(int n_calls, const void* const* xt, const void* const* zt, const int* k_in, const int* n_out,
+                             float* const* dw, float* const* db, int64_t ld, int64_t rows, const int32_t* count,
+                             void* partial, size_t partial_bytes, void* stream) {
+    std::vector<nfx_wgrad_call> calls;
+    if (int rc = selftest_wgrad_table("nfx_selftest_wgrad_batch", n_calls, k_in, n_out, rows, &calls)) return rc;
+    REQUIRE(xt && zt && dw && db, "nfx_selftest_wgrad_batch: null table");
+    // a 16-byte piece is 4 rows of one feature pair at element (pair * ld + row) * 2: ld % 4 keeps every pair's row 0 aligned
+    REQUIRE(ld >= rows && ld % 4 == 0, "nfx_selftest_wgrad_batch: ld (%lld) must be >= rows (%lld) and a multiple of 4",
+            (long long)ld, (long long)rows);
+    if (rows == 0) return NFX_OK;
+    for (int i = 0; i < n_calls; ++i) {
+        REQUIRE(xt[i] && zt[i] && dw[i], "nfx_selftest_wgrad_batch: call %d: null pointer", i);
+        if (!ALIGNED(xt[i], 16) || !ALIGNED(zt[i], 16) || !ALIGNED(dw[i], 4) || !ALIGNED(db[i], 4))
+            return nfx_fail(NFX_EALIGN, "nfx_selftest_wgrad_batch: call %d: xt and zt must be 16-byte, dw and db 4-byte aligned", i);
+        calls[i] = nfx_wgrad_call{xt[i], zt[i], k_in[i], n_out[i], dw[i], db[i]};
+    }
+    const size_t need = nfx_wgrad_partial_bytes(calls.data(), n_calls, rows);
+    REQUIRE(partial && partial_bytes >= need, "nfx_selftest_wgrad_batch: partial-sum workspace too small (%zu < %zu)",
+            partial ? partial_bytes : (size_t)0, need);
+    if (!ALIGNED(partial, 16) || !ALIGNED(count, 4))
+        return nfx_fail(NFX_EALIGN, "nfx_selftest_wgrad_batch: the workspace must be 16-byte, count 4-byte aligned");
+    if (count) {
+        int form, n_slabs;
+        long long slab;
+        nfx_wgrad_plan_of(calls.data(), n_calls, rows, &form, &slab, &n_slabs);
+        REQUIRE(form == 2, "nfx_selftest_wgrad_batch: only the wide LDS form reads a device-side row count");
+    }
+    return nfx_hip_result(nfx_launch_wgrad_batch_counted(calls.data(), n_calls, ld, rows, partial, count, (hipStream_t)stream),
+                          "wgrad");
+}
 }  // extern "C"

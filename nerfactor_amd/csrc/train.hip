@@ -657,6 +657,15 @@ int nfx_launch_wgrad_batch(const nfx_wgrad_call* calls, int n_calls, long long l
                            hipStream_t st) {
     return nfx_launch_wgrad_batch_counted(calls, n_calls, ld, rows, partial, nullptr, st);
 }
+// what nfx_launch_wgrad_batch_counted does with (calls, rows) under the current options, for the self-test entries of
+// capi_train.cpp (host only).  *form: 0 = wgrad_kernel | 1 = wgrad_lds_narrow_kernel | 2 = wgrad_lds_kernel
+void nfx_wgrad_plan_of(const nfx_wgrad_call* calls, int n_calls, long long rows, int* form, long long* slab, int* n_slabs) {
+    bool lds;
+    const int wide_blocks = wg_wide_blocks(calls, n_calls);
+    wgrad_plan(rows, wide_blocks, &lds, slab, n_slabs);
+    *form = !lds ? 0 : wide_blocks == 0 ? 1 : 2;
+}
+int nfx_wgrad_max_calls(void) { return nfx::kWgMaxCalls; }
 // whether a batch of `rows` rows takes the wide LDS form (the one that can read its row count from the device)
 int nfx_wgrad_counted_ok(long long rows) {
     bool lds;

@@ -588,6 +588,38 @@ def selftest_sincos(x, which):
     return out
 
 
+def _wgrad_dims(dims):
+    n = len(dims)
+    return n, (ctypes.c_int * n)(*[int(d[0]) for d in dims]), (ctypes.c_int * n)(*[int(d[1]) for d in dims])
+
+
+def selftest_wgrad_plan(dims, rows):
+    """dims: [(k_in, n_out), ...] of a weight-gradient batch -> {'use_lds', 'wide', 'slab', 'n_slabs'} under the current
+    options.  Host only."""
+    n, k, o = _wgrad_dims(dims)
+    use_lds, wide, n_slabs, slab = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+    check(lib.nfx_selftest_wgrad_plan(n, k, o, int(rows), ctypes.byref(use_lds), ctypes.byref(wide), ctypes.byref(slab),
+                                      ctypes.byref(n_slabs)), 'nfx_selftest_wgrad_plan')
+    return {'use_lds': bool(use_lds.value), 'wide': bool(wide.value), 'slab': slab.value, 'n_slabs': n_slabs.value}
+
+
+def selftest_wgrad_partial_bytes(dims, rows):
+    """Bytes of partial-sum workspace selftest_wgrad_batch needs for dims = [(k_in, n_out), ...].  Host only."""
+    n, k, o = _wgrad_dims(dims)
+    return int(lib.nfx_selftest_wgrad_partial_bytes(n, k, o, int(rows)))
+
+
+def selftest_wgrad_batch(calls, ld, rows, partial, count=None, partial_bytes=None):
+    """calls: [(xt, zt, k_in, n_out, dw, db | None), ...] — xt / zt feature-pair-major bf16 [ceil(F / 2), ld, 2], dw / db fp32,
+    accumulated into (include/nfx.h: nfx_selftest_wgrad_batch).  Tensors are taken as they are (views included)."""
+    n, k, o = _wgrad_dims([(c[2], c[3]) for c in calls])
+    col = lambda j: (ctypes.c_void_p * n)(*[None if c[j] is None else c[j].data_ptr() for c in calls])
+    if partial_bytes is None:
+        partial_bytes = partial.numel() * partial.element_size()
+    check(lib.nfx_selftest_wgrad_batch(n, col(0), col(1), k, o, col(4), col(5), int(ld), int(rows), _ptr(count), _ptr(partial),
+                                       int(partial_bytes), _stream()), 'nfx_selftest_wgrad_batch')
+
+
 # ------------------------------------------------------------------------- NeRFactor ops
 def mlp128_xyz_fwd(xyz, blob, out_dim, out_act=None, xyz_scale=1., post_scale=1., post_bias=0.,
                    prec='bf16'):
