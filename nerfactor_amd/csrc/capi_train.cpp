@@ -583,6 +583,7 @@ int nfx_brdf_rows_bwd(const float* z, int z_dim, const float* rusink, int64_t n,
 int nfx_launch_shade_bwd(const float*, const float*, const float*, const float*, const float*, const float*, float,
                          float, const float*, const float*, const float*, const float*, long long, int, int,
                          const float*, float*, float*, float*, float*, float*, float*, void*, hipStream_t);
+size_t nfx_shade_bwd_lds_bytes(int n_lights, int with_light_grad);   // what the launcher allocates (shade.hip)
 
 size_t nfx_shade_bwd_workspace_bytes(int n_lights) { return n_lights > 0 ? sizeof(long long) * 3 * (size_t)n_lights : 0; }
 
@@ -592,7 +593,9 @@ int nfx_shade_bwd(const float* xyz, const float* cam, const float* normal, const
                   const float* drgb, float* d_albedo, float* d_rough, float* d_spec, float* d_normal, float* d_lvis,
                   float* d_light, void* workspace, size_t workspace_bytes, void* stream) {
     REQUIRE(n >= 0 && n_lights > 0, "nfx_shade_bwd: bad shape");
-    REQUIRE((size_t)7 * n_lights * sizeof(float) <= 160 * 1024, "nfx_shade_bwd: too many lights (%d)", n_lights);
+    REQUIRE(nfx_shade_bwd_lds_bytes(n_lights, d_light != nullptr) <= 160 * 1024,
+            "nfx_shade_bwd: too many lights (%d) for the 160 KiB LDS%s", n_lights,
+            d_light ? " with a light gradient (28 + 24 bytes per light)" : " (28 bytes per light)");
     if (n == 0) return NFX_OK;
     REQUIRE(xyz && cam && normal && albedo && lvis && lxyz && lareas && light && drgb, "nfx_shade_bwd: null input");
     REQUIRE(rough || spec, "nfx_shade_bwd: need roughness (microfacet) or a specular term");

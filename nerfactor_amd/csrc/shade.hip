@@ -417,6 +417,12 @@ __device__ __forceinline__ float microfacet_spec_grad(const MicrofacetPoint& mp,
 // unit: resolution 9e-13, range +-8e6): integer addition is associative, so the result does not depend on the order the
 // atomics land in — two runs of a training step give the same bits (float atomics did not).
 constexpr double kLightFxScale = 1099511627776.0;
+// LDS: lxyz[L*3] | area[L] | light[L*3] | (pad to 8 bytes) | dl[L*3] 64-bit, the last only with a light gradient.  The kernel's
+// carve-up, the launcher's allocation and the argument check of nfx_shade_bwd all come from these two.
+__host__ __device__ constexpr size_t shade_bwd_fx_offset_floats(int n_lights) { return ((size_t)7 * n_lights + 1) / 2 * 2; }
+__host__ __device__ constexpr size_t shade_bwd_lds_bytes(int n_lights, bool with_light_grad) {
+    return sizeof(float) * shade_bwd_fx_offset_floats(n_lights) + (with_light_grad ? sizeof(long long) * (size_t)3 * n_lights : 0);
+}
 __global__ void light_fx_finish_kernel(const long long* __restrict__ fx, float* __restrict__ d_light, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) d_light[i] += (float)((double)fx[i] / kLightFxScale);
@@ -433,7 +439,7 @@ __global__ __launch_bounds__(kShadeWaves * 64) void shade_bwd_kernel(ShadeBwdArg
     // (ray, light, channel) term to HBM as its own 64-bit device-scope atomic — 1.6 M of them on 1536 addresses per
     // 1024-ray step, which the memory side serialises: 130 us of a 1.3 ms training step for a 14-us forward.  The sums are
     // integers: adding them here first (ds_add_u64) and once per workgroup to the global buffer gives the same bits.
-    unsigned long long* dl_s = reinterpret_cast<unsigned long long*>(sm + (7 * L + 1) / 2 * 2);
+    unsigned long long* dl_s = reinterpret_cast<unsigned long long*>(sm + shade_bwd_fx_offset_floats(L));
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int i = tid; i < 3 * L; i += blockDim.x) lxyz_s[i] = f.lxyz[i];
     for (int i = tid; i < L; i += blockDim.x) area_s[i] = f.lareas[i];
@@ -535,6 +541,9 @@ __global__ __launch_bounds__(kShadeWaves * 64) void shade_bwd_kernel(ShadeBwdArg
 
 }  // namespace nfx
 
+extern "C" size_t nfx_shade_bwd_lds_bytes(int n_lights, int with_light_grad) {
+    return nfx::shade_bwd_lds_bytes(n_lights, with_light_grad != 0);
+}
 extern "C" int nfx_launch_shade_bwd(const float* xyz, const float* cam, const float* normal, const float* albedo,
                                     const float* rough, const float* spec, float spec_scale, float f0,
                                     const float* lvis, const float* lxyz, const float* lareas, const float* light,
@@ -549,7 +558,7 @@ extern "C" int nfx_launch_shade_bwd(const float* xyz, const float* cam, const fl
     a.d_lvis = d_lvis;
     a.d_light_fx = d_light ? static_cast<long long*>(workspace) : nullptr;
     if (a.d_light_fx) nfx::launch_zero_words(workspace, 3ll * n_lights, st);   // (a kernel, not hipMemsetAsync: nfx_common.hpp)
-    const size_t lds = sizeof(float) * (size_t)((7 * n_lights + 1) / 2 * 2) + (d_light ? sizeof(long long) * (size_t)3 * n_lights : 0);
+    const size_t lds = nfx_shade_bwd_lds_bytes(n_lights, d_light != nullptr);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(nfx::shade_bwd_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
