@@ -113,7 +113,9 @@ def build(force=False, verbose=False, out=None):
         rebuilt = any(r for _, r in results)
         if rebuilt or not os.path.exists(LIB):
             tmp = LIB + '.tmp.%d' % os.getpid()
-            cmd = [HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC',
+            # --no-undefined: a function declared (csrc/launchers.hpp, capi_common.hpp) and called but defined nowhere, or
+            # defined under another C++ signature, fails the link here and not when the library is loaded
+            cmd = [HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', '-Wl,--no-undefined',
                    '-Wl,--version-script=' + os.path.join(CSRC, 'libnfx.map')] + objs + ['-o', tmp]
             if verbose:
                 print(' '.join(cmd), flush=True)

@@ -13,6 +13,7 @@
 #include "mlp128_layout.hpp"
 #include "mlp_engine.hpp"
 #include "feat_store.hpp"
+#include "launchers.hpp"
 
 namespace nfx {
 namespace brdfbwd {

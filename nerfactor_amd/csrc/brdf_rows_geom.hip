@@ -18,6 +18,7 @@
 #include "geom_ad.hpp"
 #include "nfx_common.hpp"
 #include "brdf_rows_geom.hpp"
+#include "launchers.hpp"
 
 namespace nfx {
 namespace rowsgeom {

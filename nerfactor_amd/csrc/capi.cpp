@@ -9,7 +9,7 @@
 #include <atomic>
 #include <vector>
 
-#include "../../include/nfx.h"
+#include "capi_common.hpp"
 #include "nerf_layout.hpp"
 #include "nerf_fold_layout.hpp"
 #include "pack.hpp"
@@ -23,44 +23,12 @@ int nfx_fail(int code, const char* fmt, ...) {
     va_end(ap);
     return code;
 }
-#define fail nfx_fail
-int nfx_hip_result(int e, const char* what);
-#define hip_result nfx_hip_result
 int nfx_hip_result(int e, const char* what) {
     if (e == 0) return NFX_OK;
-    return fail(NFX_EHIP, "%s: HIP error %d (%s)", what, e, hipGetErrorString((hipError_t)e));
+    return nfx_fail(NFX_EHIP, "%s: HIP error %d (%s)", what, e, hipGetErrorString((hipError_t)e));
 }
-#define REQUIRE(cond, ...) \
-    do {                   \
-        if (!(cond)) return fail(NFX_EINVAL, __VA_ARGS__); \
-    } while (0)
-#define ALIGNED(p, a) ((((uintptr_t)(p)) & ((a)-1)) == 0)
 
 extern "C" {
-// launchers (defined in the .hip files)
-int nfx_launch_nerf_mlp_bf16(const float*, const float*, const float*, long long, int, const void*,
-                             float*, int, int, hipStream_t);
-int nfx_launch_nerf_mlp_x3(const float*, const float*, const float*, long long, int, const void*, float*, int,
-                           hipStream_t);
-int nfx_launch_nerf_mlp_bf16_v6(const float*, const float*, const float*, long long, int, const void*, float*, int,
-                                int, hipStream_t);
-int nfx_launch_nerf_fold(const void*, void*, hipStream_t);
-int nfx_launch_nerf_mlp_bf16_fold(const float*, const float*, const float*, long long, int, const void*, float*, int, int,
-                                  hipStream_t);
-int nfx_launch_nerf_mlp_bf16_v6_fold(const float*, const float*, const float*, long long, int, const void*, float*, int,
-                                     int, hipStream_t);
-int nfx_launch_l2_normalize3(const float*, float*, long long, float, hipStream_t);
-int nfx_launch_nonfinite(const float*, long long, int*, hipStream_t);
-int nfx_launch_gen_z(float, float, int, long long, int, const float*, float*, hipStream_t);
-int nfx_launch_composite(const float*, const float*, const float*, const float*, long long, int, int,
-                         float*, float*, float*, float*, float*, hipStream_t);
-int nfx_launch_sample_fine(const float*, const float*, long long, int, int, const float*, float*,
-                           hipStream_t);
-int nfx_launch_surface(const float*, const float*, const float*, const float*, long long, int, float, int, float*, float*,
-                       float*, float*, hipStream_t);
-int nfx_launch_selftest_mfma(const float*, const float*, float*, hipStream_t);
-int nfx_launch_selftest_sincos(const float*, long long, int, float*, hipStream_t);
-
 int nfx_version(void) { return 100; }
 
 int nfx_last_error(char* buf, size_t len) {
@@ -128,25 +96,24 @@ int nfx_option_int(const char* key, int dflt) {   // internal (hidden): the valu
 }
 int nfx_set_option(const char* key, int value) {
     Option* o = find_option(key);
-    if (!o) return fail(NFX_EINVAL, "nfx_set_option: unknown option '%s'", key ? key : "(null)");
+    if (!o) return nfx_fail(NFX_EINVAL, "nfx_set_option: unknown option '%s'", key ? key : "(null)");
     o->value.store(value, std::memory_order_relaxed);
     o->is_set.store(1, std::memory_order_release);
     return NFX_OK;
 }
 int nfx_unset_option(const char* key) {
     Option* o = find_option(key);
-    if (!o) return fail(NFX_EINVAL, "nfx_unset_option: unknown option '%s'", key ? key : "(null)");
+    if (!o) return nfx_fail(NFX_EINVAL, "nfx_unset_option: unknown option '%s'", key ? key : "(null)");
     o->is_set.store(0, std::memory_order_release);
     return NFX_OK;
 }
 int nfx_get_option(const char* key, int* value, int* is_set) {
     Option* o = find_option(key);
-    if (!o || !value) return fail(NFX_EINVAL, "nfx_get_option: unknown option '%s' or null output", key ? key : "(null)");
+    if (!o || !value) return nfx_fail(NFX_EINVAL, "nfx_get_option: unknown option '%s' or null output", key ? key : "(null)");
     *value = o->value.load(std::memory_order_relaxed);
     if (is_set) *is_set = o->is_set.load(std::memory_order_acquire);
     return NFX_OK;
 }
-#define env_int nfx_option_int
 
 // --------------------------------------------------------------------------- packing
 size_t nfx_nerf_packed_bytes(int prec) {
@@ -196,7 +163,7 @@ int nfx_nerf_pack_weights(const float* const kernels[12], const float* const bia
     uint8_t* w = static_cast<uint8_t*>(blob);
     if (prec == NFX_PREC_BF16) {
         if (pack_nerf_fragments(kernels, biases, w, reinterpret_cast<float*>(w + nerf::kWeightBytes)))
-            return fail(NFX_EINVAL, "nfx_nerf_pack_weights: internal layout mismatch");
+            return nfx_fail(NFX_EINVAL, "nfx_nerf_pack_weights: internal layout mismatch");
         return NFX_OK;
     }
     // NFX_PREC_FP32 (nerf_mlp_x3.hip): [fragments of hi = bf16(W) | fragments of lo = bf16(W - hi) | fp32 biases]
@@ -219,7 +186,7 @@ int nfx_nerf_pack_weights(const float* const kernels[12], const float* const bia
     std::vector<float> sink(nerf::kBiasFloats);
     if (pack_nerf_fragments(kernels, biases, w, b) ||
         pack_nerf_fragments(lo_ptr, biases, w + nerf::kWeightBytes, sink.data()))
-        return fail(NFX_EINVAL, "nfx_nerf_pack_weights: internal layout mismatch");
+        return nfx_fail(NFX_EINVAL, "nfx_nerf_pack_weights: internal layout mismatch");
     return NFX_OK;
 }
 
@@ -227,7 +194,7 @@ int nfx_nerf_pack_weights(const float* const kernels[12], const float* const bia
 int nfx_l2_normalize3(const float* in, float* out, int64_t n, float eps, void* stream) {
     REQUIRE(n >= 0, "nfx_l2_normalize3: n < 0");
     REQUIRE(n == 0 || (in && out), "nfx_l2_normalize3: null pointer");
-    return hip_result(nfx_launch_l2_normalize3(in, out, n, eps, (hipStream_t)stream), "l2_normalize3");
+    return nfx_hip_result(nfx_launch_l2_normalize3(in, out, n, eps, (hipStream_t)stream), "l2_normalize3");
 }
 
 int nfx_any_nonfinite(const float* x, int64_t n, int* flag, void* stream) {
@@ -236,10 +203,9 @@ int nfx_any_nonfinite(const float* x, int64_t n, int* flag, void* stream) {
     if (n == 0) return NFX_OK;
     REQUIRE(x, "nfx_any_nonfinite: null tensor");
     if (!ALIGNED(x, 16)) return nfx_fail(NFX_EALIGN, "nfx_any_nonfinite: tensor must be 16-byte aligned");
-    return hip_result(nfx_launch_nonfinite(x, n, flag, (hipStream_t)stream), "any_nonfinite");
+    return nfx_hip_result(nfx_launch_nonfinite(x, n, flag, (hipStream_t)stream), "any_nonfinite");
 }
 
-int nfx_launch_scatter_rows(const float*, const int*, long long, int, float*, hipStream_t);
 int nfx_scatter_rows(const float* src, const int32_t* row_of, int64_t n_all, int d, float* dst, void* stream) {
     REQUIRE(n_all >= 0 && d >= 1, "nfx_scatter_rows: bad shape (%lld rows of %d)", (long long)n_all, d);
     if (n_all == 0) return NFX_OK;
@@ -249,8 +215,8 @@ int nfx_scatter_rows(const float* src, const int32_t* row_of, int64_t n_all, int
     const long long per_row = d % 4 == 0 ? d / 4 : d, max_rows = (1ll << 31) / per_row > 0 ? (1ll << 31) / per_row : 1;
     for (long long r0 = 0; r0 < n_all; r0 += max_rows) {
         const long long nr = n_all - r0 < max_rows ? n_all - r0 : max_rows;
-        const int rc = hip_result(nfx_launch_scatter_rows(src, row_of + r0, nr, d, dst + r0 * d, (hipStream_t)stream),
-                                  "scatter_rows");
+        const int rc = nfx_hip_result(nfx_launch_scatter_rows(src, row_of + r0, nr, d, dst + r0 * d, (hipStream_t)stream),
+                                      "scatter_rows");
         if (rc) return rc;
     }
     return NFX_OK;
@@ -261,8 +227,8 @@ int nfx_gen_z(float near, float far, int n_samples, int64_t n_rays, int lin_in_d
     REQUIRE(n_samples >= 2, "nfx_gen_z: n_samples must be >= 2 (got %d)", n_samples);
     REQUIRE(n_rays >= 0, "nfx_gen_z: n_rays < 0");
     REQUIRE(n_rays == 0 || z, "nfx_gen_z: null output");
-    return hip_result(nfx_launch_gen_z(near, far, n_samples, n_rays, lin_in_disp, u, z, (hipStream_t)stream),
-                      "gen_z");
+    return nfx_hip_result(nfx_launch_gen_z(near, far, n_samples, n_rays, lin_in_disp, u, z, (hipStream_t)stream),
+                          "gen_z");
 }
 
 int nfx_nerf_mlp_fwd(const float* rayo, const float* rayd, const float* z, int64_t n_rays, int n_samples,
@@ -272,39 +238,39 @@ int nfx_nerf_mlp_fwd(const float* rayo, const float* rayd, const float* z, int64
     if (n_rays == 0) return NFX_OK;
     REQUIRE(rayo && rayd && z && blob && rgbs, "nfx_nerf_mlp_fwd: null pointer");
     if (!ALIGNED(blob, 16) || !ALIGNED(rgbs, 16))
-        return fail(NFX_EALIGN, "nfx_nerf_mlp_fwd: blob and rgbs must be 16-byte aligned");
+        return nfx_fail(NFX_EALIGN, "nfx_nerf_mlp_fwd: blob and rgbs must be 16-byte aligned");
     const long long n_pts = (long long)n_rays * n_samples;
-    const int blocks = env_int("nerf_blocks", 256);
+    const int blocks = nfx_option_int("nerf_blocks", 256);
     if (prec == NFX_PREC_BF16) {
         // NFX_NERF_VARIANT: 7 (default) = one wave per SIMD, 64 points per wave, epilogue software-pipelined under the
         // next tile's MFMAs, weight stream by LDS-DMA into a 6-slot ring (nerf_mlp_v6.hip); 6 / 8 = the same kernel
         // with register-staged weights (one / two staging sets); 1 = the 8 waves x 32 points reference geometry with
         // two waves per SIMD, 0 = 4 x 64 plain (nerf_mlp.hip).  All bit-identical.  The intermediate variants 2, 3, 5
         // of r01 are in the git history (not built).
-        const int variant = env_int("nerf_variant", 7);
+        const int variant = nfx_option_int("nerf_variant", 7);
         if (variant == 8)
-            return hip_result(nfx_launch_nerf_mlp_bf16_v6(rayo, rayd, z, n_pts, n_samples, blob, rgbs, blocks, 2,
-                                                          (hipStream_t)stream),
-                              "nerf_mlp_fwd(bf16, v8)");
+            return nfx_hip_result(nfx_launch_nerf_mlp_bf16_v6(rayo, rayd, z, n_pts, n_samples, blob, rgbs, blocks, 2,
+                                                              (hipStream_t)stream),
+                                  "nerf_mlp_fwd(bf16, v8)");
         if (variant == 7)
-            return hip_result(nfx_launch_nerf_mlp_bf16_v6(rayo, rayd, z, n_pts, n_samples, blob, rgbs, blocks,
-                                                          1,
-                                                          (hipStream_t)stream),
-                              "nerf_mlp_fwd(bf16, v7)");
+            return nfx_hip_result(nfx_launch_nerf_mlp_bf16_v6(rayo, rayd, z, n_pts, n_samples, blob, rgbs, blocks,
+                                                              1,
+                                                              (hipStream_t)stream),
+                                  "nerf_mlp_fwd(bf16, v7)");
         if (variant == 6)
-            return hip_result(nfx_launch_nerf_mlp_bf16_v6(rayo, rayd, z, n_pts, n_samples, blob, rgbs, blocks,
-                                                          0, (hipStream_t)stream),
-                              "nerf_mlp_fwd(bf16, v6)");
+            return nfx_hip_result(nfx_launch_nerf_mlp_bf16_v6(rayo, rayd, z, n_pts, n_samples, blob, rgbs, blocks,
+                                                              0, (hipStream_t)stream),
+                                  "nerf_mlp_fwd(bf16, v6)");
         if (variant != 0 && variant != 1)
-            return fail(NFX_EINVAL, "nfx_nerf_mlp_fwd: NFX_NERF_VARIANT %d is not built (0, 1, 6, 7, 8)", variant);
-        return hip_result(nfx_launch_nerf_mlp_bf16(rayo, rayd, z, n_pts, n_samples, blob, rgbs, variant,
-                                                   blocks, (hipStream_t)stream),
-                          "nerf_mlp_fwd(bf16)");
+            return nfx_fail(NFX_EINVAL, "nfx_nerf_mlp_fwd: NFX_NERF_VARIANT %d is not built (0, 1, 6, 7, 8)", variant);
+        return nfx_hip_result(nfx_launch_nerf_mlp_bf16(rayo, rayd, z, n_pts, n_samples, blob, rgbs, variant,
+                                                       blocks, (hipStream_t)stream),
+                              "nerf_mlp_fwd(bf16)");
     }
     if (prec == NFX_PREC_FP32)  // split-bf16 operands, 3 MFMAs per product (nerf_mlp_x3.hip)
-        return hip_result(nfx_launch_nerf_mlp_x3(rayo, rayd, z, n_pts, n_samples, blob, rgbs, blocks, (hipStream_t)stream),
-                          "nerf_mlp_fwd(fp32 via 3 x bf16)");
-    return fail(NFX_EINVAL, "nfx_nerf_mlp_fwd: bad prec %d", prec);
+        return nfx_hip_result(nfx_launch_nerf_mlp_x3(rayo, rayd, z, n_pts, n_samples, blob, rgbs, blocks, (hipStream_t)stream),
+                              "nerf_mlp_fwd(fp32 via 3 x bf16)");
+    return nfx_fail(NFX_EINVAL, "nfx_nerf_mlp_fwd: bad prec %d", prec);
 }
 
 // ---- the bottleneck folded into rgb_out[0] (nerf_fold.hip, nerf_fold_layout.hpp)
@@ -315,11 +281,11 @@ int nfx_nerf_fold_blob(const void* blob, void* workspace, size_t workspace_bytes
     REQUIRE(workspace_bytes >= nfx_nerf_fold_workspace_bytes(), "nfx_nerf_fold_blob: workspace too small (%zu < %zu)",
             workspace_bytes, nfx_nerf_fold_workspace_bytes());
     if (!ALIGNED(blob, 16) || !ALIGNED(workspace, 16))
-        return fail(NFX_EALIGN, "nfx_nerf_fold_blob: blob and workspace must be 16-byte aligned");
+        return nfx_fail(NFX_EALIGN, "nfx_nerf_fold_blob: blob and workspace must be 16-byte aligned");
     const uintptr_t b = (uintptr_t)blob, w = (uintptr_t)workspace;
     REQUIRE(b + nfx::nerf::kBlobBytes <= w || w + nfx_nerf_fold_workspace_bytes() <= b,
             "nfx_nerf_fold_blob: the workspace overlaps the blob");
-    return hip_result(nfx_launch_nerf_fold(blob, workspace, (hipStream_t)stream), "nerf_fold_blob");
+    return nfx_hip_result(nfx_launch_nerf_fold(blob, workspace, (hipStream_t)stream), "nerf_fold_blob");
 }
 
 int nfx_nerf_mlp_fwd_folded(const float* rayo, const float* rayd, const float* z, int64_t n_rays, int n_samples,
@@ -328,22 +294,22 @@ int nfx_nerf_mlp_fwd_folded(const float* rayo, const float* rayd, const float* z
             (long long)n_rays, n_samples);
     if (n_rays == 0) return NFX_OK;
     REQUIRE(rayo && rayd && z && blob && rgbs, "nfx_nerf_mlp_fwd_folded: null pointer");
-    if (!ALIGNED(rgbs, 16)) return fail(NFX_EALIGN, "nfx_nerf_mlp_fwd_folded: rgbs must be 16-byte aligned");
+    if (!ALIGNED(rgbs, 16)) return nfx_fail(NFX_EALIGN, "nfx_nerf_mlp_fwd_folded: rgbs must be 16-byte aligned");
     // folded on every call, never cached: blobs are re-packed in place on the device while a network trains
     const int rc = nfx_nerf_fold_blob(blob, workspace, workspace_bytes, stream);
     if (rc) return rc;
     const long long n_pts = (long long)n_rays * n_samples;
-    const int blocks = env_int("nerf_blocks", 256);
-    const int variant = env_int("nerf_variant", 7);   // as nfx_nerf_mlp_fwd; all bit-identical to each other
+    const int blocks = nfx_option_int("nerf_blocks", 256);
+    const int variant = nfx_option_int("nerf_variant", 7);   // as nfx_nerf_mlp_fwd; all bit-identical to each other
     if (variant == 6 || variant == 7 || variant == 8)
-        return hip_result(nfx_launch_nerf_mlp_bf16_v6_fold(rayo, rayd, z, n_pts, n_samples, workspace, rgbs, blocks,
-                                                           variant == 8 ? 2 : variant == 7 ? 1 : 0, (hipStream_t)stream),
-                          "nerf_mlp_fwd_folded(bf16, v6-8)");
+        return nfx_hip_result(nfx_launch_nerf_mlp_bf16_v6_fold(rayo, rayd, z, n_pts, n_samples, workspace, rgbs, blocks,
+                                                               variant == 8 ? 2 : variant == 7 ? 1 : 0, (hipStream_t)stream),
+                              "nerf_mlp_fwd_folded(bf16, v6-8)");
     if (variant != 0 && variant != 1)
-        return fail(NFX_EINVAL, "nfx_nerf_mlp_fwd_folded: NFX_NERF_VARIANT %d is not built (0, 1, 6, 7, 8)", variant);
-    return hip_result(nfx_launch_nerf_mlp_bf16_fold(rayo, rayd, z, n_pts, n_samples, workspace, rgbs, variant, blocks,
-                                                    (hipStream_t)stream),
-                      "nerf_mlp_fwd_folded(bf16)");
+        return nfx_fail(NFX_EINVAL, "nfx_nerf_mlp_fwd_folded: NFX_NERF_VARIANT %d is not built (0, 1, 6, 7, 8)", variant);
+    return nfx_hip_result(nfx_launch_nerf_mlp_bf16_fold(rayo, rayd, z, n_pts, n_samples, workspace, rgbs, variant, blocks,
+                                                        (hipStream_t)stream),
+                          "nerf_mlp_fwd_folded(bf16)");
 }
 
 int nfx_composite_fwd(const float* rgbs, const float* z, const float* rayd, const float* noise,
@@ -352,10 +318,10 @@ int nfx_composite_fwd(const float* rgbs, const float* z, const float* rayd, cons
     REQUIRE(n_rays >= 0 && n_samples >= 1, "nfx_composite_fwd: bad shape");
     if (n_rays == 0) return NFX_OK;
     REQUIRE(rgbs && z && rayd, "nfx_composite_fwd: null input");
-    if (!ALIGNED(rgbs, 16)) return fail(NFX_EALIGN, "nfx_composite_fwd: rgbs must be 16-byte aligned");
-    return hip_result(nfx_launch_composite(rgbs, z, rayd, noise, n_rays, n_samples, white_bg, rgb, occu,
-                                           depth, disp, weights, (hipStream_t)stream),
-                      "composite_fwd");
+    if (!ALIGNED(rgbs, 16)) return nfx_fail(NFX_EALIGN, "nfx_composite_fwd: rgbs must be 16-byte aligned");
+    return nfx_hip_result(nfx_launch_composite(rgbs, z, rayd, noise, n_rays, n_samples, white_bg, rgb, occu,
+                                               depth, disp, weights, (hipStream_t)stream),
+                          "composite_fwd");
 }
 
 int nfx_nerf_surface_fwd(const float* sigma, const float* z, const float* rayo, const float* rayd, int64_t n_rays,
@@ -367,9 +333,9 @@ int nfx_nerf_surface_fwd(const float* sigma, const float* z, const float* rayo, 
     if (n_rays == 0) return NFX_OK;
     REQUIRE(sigma && z && rayo && rayd, "nfx_nerf_surface_fwd: null input");
     REQUIRE(alpha && xyz && depth, "nfx_nerf_surface_fwd: null output (only occu may be NULL)");
-    return hip_result(nfx_launch_surface(sigma, z, rayo, rayd, n_rays, n_samples, occu_thres, quantize_alpha ? 1 : 0, alpha,
-                                         xyz, depth, occu, (hipStream_t)stream),
-                      "nerf_surface_fwd");
+    return nfx_hip_result(nfx_launch_surface(sigma, z, rayo, rayd, n_rays, n_samples, occu_thres, quantize_alpha ? 1 : 0, alpha,
+                                             xyz, depth, occu, (hipStream_t)stream),
+                          "nerf_surface_fwd");
 }
 
 int nfx_sample_fine(const float* z, const float* weights, int64_t n_rays, int n_coarse, int n_fine,
@@ -382,24 +348,23 @@ int nfx_sample_fine(const float* z, const float* weights, int64_t n_rays, int n_
             "nfx_sample_fine: n_coarse + n_fine too large for one workgroup's LDS");
     if (n_rays == 0) return NFX_OK;
     REQUIRE(z && weights && z_all, "nfx_sample_fine: null pointer");
-    return hip_result(
-        nfx_launch_sample_fine(z, weights, n_rays, n_coarse, n_fine, u, z_all, (hipStream_t)stream),
-        "sample_fine");
+    return nfx_hip_result(
+            nfx_launch_sample_fine(z, weights, n_rays, n_coarse, n_fine, u, z_all, (hipStream_t)stream),
+            "sample_fine");
 }
 
 // --------------------------------------------------------------------- diagnostics
 int nfx_selftest_mfma_bf16(const float* a, const float* b, float* d, void* stream) {
     REQUIRE(a && b && d, "nfx_selftest_mfma_bf16: null pointer");
-    return hip_result(nfx_launch_selftest_mfma(a, b, d, (hipStream_t)stream), "selftest_mfma");
+    return nfx_hip_result(nfx_launch_selftest_mfma(a, b, d, (hipStream_t)stream), "selftest_mfma");
 }
-int nfx_launch_selftest_tr16(const float*, const float*, float*, int, hipStream_t);
 int nfx_selftest_tr16(const float* h, const float* z, float* d, int mode, void* stream) {
     REQUIRE(d && (mode == 1 || (h && z)), "nfx_selftest_tr16: null pointer");
-    return hip_result(nfx_launch_selftest_tr16(h, z, d, mode, (hipStream_t)stream), "selftest_tr16");
+    return nfx_hip_result(nfx_launch_selftest_tr16(h, z, d, mode, (hipStream_t)stream), "selftest_tr16");
 }
 int nfx_selftest_sincos(const float* in, int64_t n, int which, float* out, void* stream) {
     REQUIRE(n >= 0 && (n == 0 || (in && out)), "nfx_selftest_sincos: bad arguments");
-    return hip_result(nfx_launch_selftest_sincos(in, n, which, out, (hipStream_t)stream), "selftest_sincos");
+    return nfx_hip_result(nfx_launch_selftest_sincos(in, n, which, out, (hipStream_t)stream), "selftest_sincos");
 }
 
 }  // extern "C"

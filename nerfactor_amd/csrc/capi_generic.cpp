@@ -2,25 +2,9 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 
-#include "../../include/nfx.h"
+#include "capi_common.hpp"
 #include "mlp_generic.hpp"
 #include "pack.hpp"
-
-int nfx_fail(int code, const char* fmt, ...);                    // capi.cpp
-int nfx_hip_result(int e, const char* what);                     // capi.cpp
-extern "C" int nfx_option_int(const char* key, int dflt);        // capi.cpp
-#define REQUIRE(cond, ...) \
-    do {                   \
-        if (!(cond)) return nfx_fail(NFX_EINVAL, __VA_ARGS__); \
-    } while (0)
-
-extern "C" {
-int nfx_launch_mlp_generic(const nfx::generic::Args* args, int max_blocks, hipStream_t st);
-int nfx_launch_embed(const nfx::generic::EmbedArgs* a, hipStream_t st);
-int nfx_launch_embed_bwd(const nfx::generic::EmbedArgs* a, const float* d_out, float* dv, hipStream_t st);
-int nfx_launch_mlp_generic_bwd(const nfx::generic::BwdArgs* ba, const nfx::generic::WgradArgs* wa, int max_blocks, hipStream_t st);
-int nfx_launch_split_hilo(void* frags, long long n_frags, hipStream_t st);
-}
 
 // the layer table of a network: mlp.Network(widths, skip_at) semantics (nerfactor/networks/mlp.py:38-50) —
 // skip_input[i] != 0 <=> layer i reads concat(output of layer i - 1, network input), i.e. i - 1 is in skip_at

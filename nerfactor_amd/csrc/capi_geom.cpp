@@ -6,51 +6,11 @@
 
 #include <vector>
 
-#include "../../include/nfx.h"
+#include "capi_common.hpp"
 #include "nerf_geom_layout.hpp"
 #include "pack.hpp"
 
-int nfx_fail(int code, const char* fmt, ...);
-int nfx_hip_result(int e, const char* what);
-extern "C" int nfx_option_int(const char* name, int dflt);
-
-#define REQUIRE(cond, ...) \
-    do {                   \
-        if (!(cond)) return nfx_fail(NFX_EINVAL, __VA_ARGS__); \
-    } while (0)
-#define ALIGNED(p, a) ((((uintptr_t)(p)) & ((a)-1)) == 0)
-
 extern "C" {
-int nfx_launch_nerf_sigma_geo(const float*, const float*, const float*, long long, int, const void*, float*, int,
-                              hipStream_t);
-int nfx_launch_nerf_sigma_grad(const float*, const float*, const float*, long long, int, const void*, float*, int,
-                               hipStream_t);
-int nfx_launch_refine_select(const float*, const float*, const float*, long long, int, float, float, float, float, int, int*, int*,
-                             hipStream_t);
-int nfx_launch_nerf_sigma_v6(const float*, const float*, const float*, long long, int, const void*, float*, int, hipStream_t);
-int nfx_launch_nerf_sigma_grad_list(const float*, const float*, const float*, long long, int, const void*, float*, const int*,
-                                    const int*, int, hipStream_t);
-int nfx_launch_nerf_sigma_grad_x3_list(const float*, const float*, const float*, long long, int, const void*, float*,
-                                       const int*, const int*, int, hipStream_t);
-int nfx_launch_select_density(const float*, long long, float*, void*, hipStream_t);
-size_t nfx_nerf_bwd_list_bytes(long long n_pts);   // nerf_bwd.hip: bytes of a rowsel list over n_pts rows
-int nfx_launch_nerf_sigma_x3_list(const float*, const float*, const float*, long long, int, const void*, float*, const int*,
-                                  const int*, int, hipStream_t);
-int nfx_launch_nerf_sigma_x3(const float*, const float*, const float*, long long, int, const void*, float*, int,
-                             hipStream_t);   // nerf_geom_x3.hip
-int nfx_launch_nerf_sigma_grad_x3(const float*, const float*, const float*, long long, int, const void*, float*, int,
-                                  hipStream_t);
-int nfx_launch_nerf_sigma_v6_list(const float*, const float*, const float*, long long, int, const void*, float*, const int*,
-                                  const int*, int, hipStream_t);   // nerf_sigma_v6.hip
-int nfx_launch_nerf_sigma_x3_list_flat(const float*, const float*, const float*, long long, int, const void*, float*,
-                                       const int*, const int*, int, hipStream_t);
-int nfx_launch_nerf_sigma_x3_last(const float*, const float*, const float*, long long, int, const void*, float*, int,
-                                  hipStream_t);
-size_t nfx_occgrid_list_bytes(long long n_pts);   // occgrid.hip
-int nfx_launch_occgrid_select(const float*, const float*, const float*, long long, int, const uint32_t*, int, const float*,
-                              const float*, float*, void*, hipStream_t);
-int nfx_launch_occgrid_bake(const float*, int, int, float, int, uint32_t*, uint32_t*, hipStream_t);
-
 size_t nfx_nerf_geom_packed_bytes(int prec) {
     using namespace nfx::nerf;
     if (prec == NFX_PREC_BF16) return (size_t)kGeoBlobBytes;

@@ -7,59 +7,13 @@
 
 #include <vector>
 
-#include "../../include/nfx.h"
+#include "capi_common.hpp"
 #include "brdf_rows_geom.hpp"
 #include "mlp128_layout.hpp"
 #include "pack.hpp"
 
-int nfx_fail(int code, const char* fmt, ...);       // capi.cpp
-int nfx_hip_result(int e, const char* what);        // capi.cpp
-extern "C" int nfx_option_int(const char* name, int dflt);  // capi.cpp
-
-#define REQUIRE(cond, ...) \
-    do {                   \
-        if (!(cond)) return nfx_fail(NFX_EINVAL, __VA_ARGS__); \
-    } while (0)
-#define ALIGNED(p, a) ((((uintptr_t)(p)) & ((a)-1)) == 0)
-
 extern "C" {
-int nfx_launch_brdf_rows_geom(const nfx::rowsgeom::Args*, int, hipStream_t);
-int nfx_launch_mlp128_xyz(const float*, long long, float, const void*, int, int, float, float, float*, int,
-                          hipStream_t);
-int nfx_launch_lvis_pre(const float*, long long, float, const void*, float*, int, hipStream_t);
-int nfx_launch_brdf_spec_v2(const float*, const float*, const float*, const float*, int, const float*, int,
-                            const void*, long long, float*, int, int, hipStream_t);
-int nfx_launch_brdf_spec_v3(const float*, const float*, const float*, const float*, int, const float*, int,
-                            const void*, long long, float*, int, int, int, hipStream_t);
-int nfx_launch_lvis_v2(const float*, long long, const float*, int, const float*, const void*, float*, int, int,
-                       hipStream_t, const int*, int*);
-int nfx_launch_zero_rows(float*, const int*, long long, int, hipStream_t);
-int nfx_launch_lvis(const float*, long long, const float*, int, const float*, const void*, float*, int,
-                    hipStream_t);
-int nfx_launch_brdf_spec(const float*, const float*, const float*, const float*, int, const float*, int,
-                         const void*, long long, float*, int, hipStream_t);
-int nfx_launch_shade(const float*, const float*, const float*, const float*, const float*, const float*, float,
-                     float, const float*, const float*, const float*, const float*, long long, int, int, int,
-                     float*, hipStream_t, const int*);
-int nfx_launch_shade_olat(const float*, const float*, const float*, const float*, const float*, const float*,
-                          float, float, const float*, const float*, const float*, float, float, long long, int,
-                          int, float*, hipStream_t, const int*, const int*, int*);
-int nfx_launch_dir2rusink(const float*, const float*, long long, float*, hipStream_t);
-size_t nfx_shade_olat_lds_bytes(int n_lights);
-int nfx_mlp128_x3_weight_bytes(int in_kind);   // mlp128_x3.hip
-int nfx_launch_mlp128_x3(int, const float*, const float*, const float*, const float*, const float*, const float*, int,
-                         long long, int, float, const void*, int, int, float, float, float*, int, hipStream_t);
-
 // ------------------------------------------------------------------------------ packing
-static int in_dims_of(int in_kind, int z_dim) {
-    switch (in_kind) {
-        case NFX_IN_XYZ: return 63;
-        case NFX_IN_XYZ_LDIR: return 90;
-        case NFX_IN_Z_RUSINK: return z_dim + 15;
-        default: return -1;
-    }
-}
-
 size_t nfx_mlp128_packed_bytes(int in_kind, int z_dim, int out_dim, int prec) {
     using namespace nfx::m128;
     if (out_dim < 1 || out_dim > 8) return 0;
@@ -76,23 +30,6 @@ size_t nfx_mlp128_packed_bytes(int in_kind, int z_dim, int out_dim, int prec) {
     return 0;
 }
 
-// B-operand slot table of the learned-BRDF input [z(z_dim) | posenc2(rusink)(15)], see
-// brdf_spec_kernel in mlp128.hip: [k-step][half][element] -> input row, -1 = zero.
-static void brdf_input_slots(int zd, int* slots /*[2][2][8]*/) {
-    for (int i = 0; i < 32; ++i) slots[i] = -1;
-    for (int h = 0; h < 2; ++h) {
-        int* s0 = slots + h * 8;
-        for (int j = 0; j < 6; ++j) s0[j] = zd + 3 + 6 * (j / 3) + (j % 3) + (h ? 3 : 0);
-        s0[6] = zd + (h ? 2 : 0);
-        s0[7] = h ? 0 : zd + 1;
-        int* s1 = slots + 16 + h * 8;
-        for (int j = 0; j < 8; ++j) {
-            const int i = 1 + 2 * j + h;
-            s1[j] = i < zd ? i : -1;
-        }
-    }
-}
-
 // One half (hi or lo) of the NFX_PREC_FP32 blob: the plain five layers, the light-visibility input NOT folded.
 static int pack_m128_x3_half(const float* const kernels[5], const float* const biases[5], int in_kind, int z_dim,
                              int out_dim, uint8_t* w, float* b) {
@@ -100,7 +37,7 @@ static int pack_m128_x3_half(const float* const kernels[5], const float* const b
     const uint8_t* w0 = w;
     const Seg hid{kHidden, 128, 0, nullptr};
     int slots[32];
-    brdf_input_slots(z_dim, slots);
+    nfx::m128::brdf_input_slots(z_dim, slots);
     std::vector<Seg> in0, in3{hid};
     int p0 = 4, p3 = 12;
     if (in_kind == NFX_IN_Z_RUSINK) {
@@ -163,7 +100,7 @@ int nfx_mlp128_pack_weights(const float* const kernels[5], const float* const bi
     }
     const Seg hid{kHidden, 128, 0, nullptr};
     int slots[32];
-    brdf_input_slots(z_dim, slots);
+    nfx::m128::brdf_input_slots(z_dim, slots);
     if (in_kind == NFX_IN_XYZ_LDIR) {
         float* pb = reinterpret_cast<float*>(w + kPreWeightBytes);
         w += pack_layer_bf16({Seg{kPosEnc, 10, 0, nullptr}}, {{kernels[0], biases[0], 128}}, 4, 4, w, pb);
@@ -186,7 +123,6 @@ int nfx_mlp128_pack_weights(const float* const kernels[5], const float* const bi
         in0 = Seg{kRaw, 2, 0, slots};
         in3 = Seg{kRaw, 2, 128, slots};
     }
-    (void)in_dims;
     w += pack_layer_bf16({in0}, {{kernels[0], bias0, 128}}, 4, 4, w, b);
     w += pack_layer_bf16({hid}, {{kernels[1], biases[1], 128}}, 4, 8, w, b + 128);
     w += pack_layer_bf16({hid}, {{kernels[2], biases[2], 128}}, 4, 8, w, b + 256);

@@ -5,50 +5,13 @@
 
 #include <vector>
 
-#include "../../include/nfx.h"
+#include "capi_common.hpp"
 #include "mlp128_layout.hpp"
 #include "nerf_train_layout.hpp"
 #include "pack.hpp"
 
-int nfx_fail(int code, const char* fmt, ...);
-int nfx_hip_result(int e, const char* what);
-extern "C" int nfx_option_int(const char* name, int dflt);
-
-#define REQUIRE(cond, ...) \
-    do {                   \
-        if (!(cond)) return nfx_fail(NFX_EINVAL, __VA_ARGS__); \
-    } while (0)
-#define ALIGNED(p, a) ((((uintptr_t)(p)) & ((a)-1)) == 0)
-
 extern "C" {
-int nfx_launch_mlp128_bwd(int, const float*, const float*, long long, float, const float*, int, const void*, int,
-                          int, float, const float*, void*, long long, int, hipStream_t);
-int nfx_launch_mlp128_bwd_fused(int, const float*, const float*, long long, float, const float*, int, int, const void* const*,
-                                const int*, const int*, const float*, const float* const*, float*, int, float* const*,
-                                float* const*, hipStream_t);
-size_t nfx_mlp128_fused_partial_floats(int in_kind, int grid);
-int nfx_mlp128_fused_grid(int in_kind, long long n, int n_lights, int max_blocks);
-int nfx_mlp128_train_feats(int in_kind);
-int nfx_mlp128_train_blob_bytes(int in_kind);
-struct nfx_wgrad_call {   // one weight-gradient GEMM of a batched launch (train.hip)
-    const void* xt;
-    const void* zt;
-    int k_in, n_out;
-    float* dw;
-    float* db;
-};
-size_t nfx_wgrad_partial_bytes(const nfx_wgrad_call* calls, int n_calls, long long rows);
-int nfx_launch_wgrad_batch(const nfx_wgrad_call* calls, int n_calls, long long ld, long long rows, void* partial,
-                           hipStream_t st);
-int nfx_launch_wgrad_batch_counted(const nfx_wgrad_call* calls, int n_calls, long long ld, long long rows, void* partial,
-                                   const int* count, hipStream_t st);
-int nfx_wgrad_counted_ok(long long rows);
-int nfx_launch_amsgrad(float*, const float*, float*, float*, float*, long long, float, float, float, float,
-                       hipStream_t);
-float nfx_amsgrad_step_size(float lr, float beta1, float beta2, int64_t step);
-
 static bool kind_ok(int k) { return k == NFX_IN_XYZ || k == NFX_IN_XYZ_LDIR; }
-static int in_dims(int k) { return k == NFX_IN_XYZ ? 63 : 90; }
 
 size_t nfx_mlp128_train_packed_bytes(int in_kind) {
     return kind_ok(in_kind) ? (size_t)nfx_mlp128_train_blob_bytes(in_kind) : 0;
@@ -64,7 +27,6 @@ int nfx_mlp128_pack_train_weights(const float* const kernels[5], const float* co
     if (prec != NFX_PREC_BF16) return nfx_fail(NFX_ENOSUP, "nfx_mlp128_pack_train_weights: only bf16 is built");
     const size_t need = nfx_mlp128_train_packed_bytes(in_kind);
     REQUIRE(blob_bytes >= need, "nfx_mlp128_pack_train_weights: blob too small (%zu < %zu)", blob_bytes, need);
-    const int ind = in_dims(in_kind);
     const bool lv = in_kind == NFX_IN_XYZ_LDIR;
     const int p0 = lv ? 8 : 4, p3 = lv ? 16 : 12;
     uint8_t* w = static_cast<uint8_t*>(blob);
@@ -101,7 +63,6 @@ int nfx_mlp128_pack_train_weights(const float* const kernels[5], const float* co
         std::vector<float> t = transposed(kernels[l], 128, 128, 128);
         w += pack_layer_bf16({hid}, {{t.data(), nullptr, 128}}, 4, 8, w, bias_sink.data());
     }
-    (void)ind;
     if (w != reinterpret_cast<uint8_t*>(b)) return nfx_fail(NFX_EINVAL, "nfx_mlp128_pack_train_weights: layout mismatch");
     return NFX_OK;
 }
@@ -113,7 +74,7 @@ static long long ld_for(int in_kind, int64_t n, int n_lights) {
 
 // the six weight-gradient GEMMs of one width-128 backward (pointers filled in by the caller)
 static void mlp128_wgrad_calls(int in_kind, int out_dim, nfx_wgrad_call (&calls)[6]) {
-    const int ind = in_dims(in_kind);
+    const int ind = in_dims_of(in_kind, 0);
     const int dims[6][2] = {{ind, 128}, {128, 128}, {128, 128}, {128, 128}, {ind, 128}, {128, out_dim}};
     for (int i = 0; i < 6; ++i) calls[i] = nfx_wgrad_call{nullptr, nullptr, dims[i][0], dims[i][1], nullptr, nullptr};
 }
@@ -172,7 +133,7 @@ int nfx_mlp128_bwd(int in_kind, const float* xyz, const float* xyz_dir, int64_t 
                                                   nfx_option_int("m128_blocks", 256), st),
                             "mlp128_bwd");
     if (rc) return rc;
-    const int ind = in_dims(in_kind), kx = in_kind == NFX_IN_XYZ ? 64 : 96;
+    const int ind = in_dims_of(in_kind, 0), kx = in_kind == NFX_IN_XYZ ? 64 : 96;
     const char* ws = static_cast<const char*>(workspace);
     auto feat = [&](int f) { return ws + (size_t)f * ld * 2; };
     const int oH = kx, oDZ = kx + 512, oDZo = kx + 1024;
@@ -232,12 +193,6 @@ int nfx_mlp128_bwd_heads(int in_kind, const float* xyz, const float* xyz_dir, in
 }
 
 // ------------------------------------------------------------------------------------ NeRF MLP backward
-int nfx_launch_nerf_bwd(const float*, const float*, const float*, long long, int, const void*, const float*, void*,
-                        long long, int, hipStream_t, void*);
-size_t nfx_nerf_bwd_list_bytes(long long n_pts);
-int nfx_launch_composite_bwd(const float*, const float*, const float*, const float*, long long, int, int,
-                             const float*, float*, hipStream_t);
-
 size_t nfx_nerf_train_packed_bytes(int prec) { return prec == NFX_PREC_BF16 ? (size_t)nfx::nerf::kTrainBlobBytes : 0; }
 
 int nfx_nerf_pack_train_weights(const float* const kernels[12], const float* const biases[12], int prec, void* blob,
@@ -376,8 +331,6 @@ int nfx_composite_bwd(const float* rgbs, const float* z, const float* rayd, cons
 }
 
 // ------------------------------------------------------------------------------------ device-side re-packing
-int nfx_launch_pack_gather(const float*, const int*, long long, void*, hipStream_t);
-
 int nfx_pack_gather(const float* src, const int32_t* map, int64_t n_words, void* blob, void* stream) {
     REQUIRE(n_words >= 0, "nfx_pack_gather: negative size");
     if (n_words == 0) return NFX_OK;
@@ -387,27 +340,7 @@ int nfx_pack_gather(const float* src, const int32_t* map, int64_t n_words, void*
     return nfx_hip_result(nfx_launch_pack_gather(src, map, n_words, blob, (hipStream_t)stream), "pack_gather");
 }
 
-int nfx_brdf_train_blob_bytes(void);
-int nfx_launch_brdf_spec_bwd(const float*, const float*, const float*, const float*, int, const float*, int,
-                             const void*, long long, const float*, float*, float*, void*, int, hipStream_t, void*);
-
 size_t nfx_brdf_train_packed_bytes(void) { return (size_t)nfx_brdf_train_blob_bytes(); }
-
-// same slot table as brdf_input_slots() in capi_nerfactor.cpp / brdf_spec_kernel
-static void brdf_slots(int zd, int* slots) {
-    for (int i = 0; i < 32; ++i) slots[i] = -1;
-    for (int h = 0; h < 2; ++h) {
-        int* s0 = slots + h * 8;
-        for (int j = 0; j < 6; ++j) s0[j] = zd + 3 + 6 * (j / 3) + (j % 3) + (h ? 3 : 0);
-        s0[6] = zd + (h ? 2 : 0);
-        s0[7] = h ? 0 : zd + 1;
-        int* s1 = slots + 16 + h * 8;
-        for (int j = 0; j < 8; ++j) {
-            const int i = 1 + 2 * j + h;
-            s1[j] = i < zd ? i : -1;
-        }
-    }
-}
 
 int nfx_brdf_pack_train_weights(const float* const kernels[5], const float* const biases[5], int z_dim, int prec,
                                 void* blob, size_t blob_bytes) {
@@ -419,7 +352,7 @@ int nfx_brdf_pack_train_weights(const float* const kernels[5], const float* cons
     const size_t need = nfx_brdf_train_packed_bytes();
     REQUIRE(blob_bytes >= need, "nfx_brdf_pack_train_weights: blob too small (%zu < %zu)", blob_bytes, need);
     int slots[32];
-    brdf_slots(z_dim, slots);
+    nfx::m128::brdf_input_slots(z_dim, slots);
     uint8_t* w = static_cast<uint8_t*>(blob);
     float* b = reinterpret_cast<float*>(w + need - nfx::m128::kMainBiasFloats * 4);
     const Seg hid{kHidden, 128, 0, nullptr};
@@ -510,10 +443,6 @@ int nfx_brdf_spec_bwd_rows(const float* xyz, const float* cam, const float* norm
 }
 
 // ---------------------------------------------------------------- the BRDF prior on explicit rows (f-4)
-int nfx_brdf_rows_feats(void);
-int nfx_launch_brdf_rows(int, const float*, int, const float*, long long, long long, const void*, const float*, float*,
-                         void*, long long, int, hipStream_t);
-
 static void brdf_rows_wgrad_calls(int z_dim, nfx_wgrad_call (&calls)[6]) {
     const int ind = z_dim + 15;
     const int dims[6][2] = {{ind, 128}, {128, 128}, {128, 128}, {128, 128}, {ind, 128}, {128, 1}};
@@ -580,11 +509,6 @@ int nfx_brdf_rows_bwd(const float* z, int z_dim, const float* rusink, int64_t n,
     return nfx_hip_result(nfx_launch_wgrad_batch(calls, 6, ld, rows16, partial, st), "wgrad");
 }
 
-int nfx_launch_shade_bwd(const float*, const float*, const float*, const float*, const float*, const float*, float,
-                         float, const float*, const float*, const float*, const float*, long long, int, int,
-                         const float*, float*, float*, float*, float*, float*, float*, void*, hipStream_t);
-size_t nfx_shade_bwd_lds_bytes(int n_lights, int with_light_grad);   // what the launcher allocates (shade.hip)
-
 size_t nfx_shade_bwd_workspace_bytes(int n_lights) { return n_lights > 0 ? sizeof(long long) * 3 * (size_t)n_lights : 0; }
 
 int nfx_shade_bwd(const float* xyz, const float* cam, const float* normal, const float* albedo, const float* rough,
@@ -612,8 +536,6 @@ int nfx_shade_bwd(const float* xyz, const float* cam, const float* normal, const
                           "shade_bwd");
 }
 
-int nfx_launch_pair_loss(int, const nfx_loss_term*, int, const float*, float, long long, float*, const float*,
-                         hipStream_t);
 static int pair_loss_check(const char* who, const nfx_loss_term* terms, int n_terms, int64_t n, bool bwd) {
     REQUIRE(n >= 0, "%s: n < 0", who);
     REQUIRE(terms && n_terms >= 1 && n_terms <= NFX_LOSS_MAX_TERMS, "%s: 1..%d terms", who, NFX_LOSS_MAX_TERMS);
@@ -643,8 +565,6 @@ int nfx_pair_loss_bwd(const nfx_loss_term* terms, int n_terms, const float* alph
                           "pair_loss_bwd");
 }
 
-int nfx_launch_l2_normalize_rows(int, const float*, const float*, float*, long long, int, float, hipStream_t);
-int nfx_launch_light_smoothness(const float*, int, int, float, float, float*, float*, hipStream_t);
 int nfx_l2_normalize_rows(const float* x, float* y, int64_t n, int d, float eps, void* stream) {
     REQUIRE(n >= 0 && d >= 1 && d <= 16, "nfx_l2_normalize_rows: n >= 0 and 1 <= d <= 16");
     REQUIRE(n == 0 || (x && y), "nfx_l2_normalize_rows: null pointer");
@@ -672,8 +592,6 @@ int nfx_amsgrad_step(float* p, const float* g, float* m, float* v, float* vhat, 
     return nfx_hip_result(nfx_launch_amsgrad(p, g, m, v, vhat, n, lr_t, beta1, beta2, eps, (hipStream_t)stream),
                           "amsgrad_step");
 }
-int nfx_launch_amsgrad_dev(float*, const float*, float*, float*, float*, long long, const float*, float, float, float,
-                           hipStream_t);
 float nfx_amsgrad_step_size(float lr, float beta1, float beta2, int64_t step) {
     const double b1p = pow((double)beta1, (double)step), b2p = pow((double)beta2, (double)step);
     return (float)((double)lr * sqrt(1.0 - b2p) / (1.0 - b1p));
@@ -688,9 +606,6 @@ int nfx_amsgrad_step_dev(float* p, const float* g, float* m, float* v, float* vh
 }
 
 // ---------------------------------------------------------------- self-test door to the weight-gradient batch (train.hip)
-void nfx_wgrad_plan_of(const nfx_wgrad_call*, int, long long, int*, long long*, int*);
-int nfx_wgrad_max_calls(void);
-
 // the dims of a table as a call table without pointers (what the plan and the workspace size depend on)
 static int selftest_wgrad_table(const char* who, int n_calls, const int* k_in, const int* n_out, int64_t rows,
                                 std::vector<nfx_wgrad_call>* calls) {

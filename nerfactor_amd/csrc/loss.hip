@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/nfx.h"
+#include "launchers.hpp"
 
 namespace nfx {
 

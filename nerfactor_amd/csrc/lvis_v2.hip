@@ -12,6 +12,7 @@
 #include "geom.hpp"
 #include "mlp128_layout.hpp"
 #include "mlp_engine.hpp"
+#include "launchers.hpp"
 
 namespace nfx {
 namespace lv2 {
@@ -311,7 +312,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void resident128_kernel(Args a) {
                 mat3_apply(rot, vdir, vl);
                 dir2rusink(ll, vl, rus);      // util/geom.py:152-192 with a = light, b = view
                 front[c] = ll[2] > 0.0f;      // nerfactor.py:429-432
-                // B operand slots of brdf_input_slots() (capi_nerfactor.cpp)
+                // B operand slots of brdf_input_slots() (mlp128_layout.hpp)
                 float v[16];
 #pragma unroll
                 for (int q = 0; q < 6; ++q) v[q] = sin_shifted_small(rus[q % 3] * (float)(1 << (q / 3)), h);   // angles <= pi, 2 bands
@@ -452,7 +453,7 @@ __device__ __forceinline__ float atan2_poly(float y, float x) {   // Cephes atan
     return y < 0.0f ? -r : r;
 }
 
-// B-operand values (slot order of brdf_input_slots(), capi_nerfactor.cpp) of one (point, light) row, lane half h
+// B-operand values (slot order of brdf_input_slots(), mlp128_layout.hpp) of one (point, light) row, lane half h
 template <int GEO>
 __device__ __forceinline__ void brdf_row_inputs(const float (&x)[3], const float (&lp)[3], const float (&cm)[3],
                                                 const float (&nr)[3], const float* zp, int z_dim, int h,

@@ -7,6 +7,7 @@
 #include "geom.hpp"
 #include "mlp128_layout.hpp"
 #include "mlp_engine.hpp"
+#include "launchers.hpp"
 
 namespace nfx {
 

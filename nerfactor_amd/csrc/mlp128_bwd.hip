@@ -17,6 +17,7 @@
 #include "mlp128_train_layout.hpp"
 #include "mlp_engine.hpp"
 #include "feat_store.hpp"
+#include "launchers.hpp"
 
 namespace nfx {
 namespace bwd {
@@ -419,8 +420,6 @@ __global__ __launch_bounds__(kNW * 64, 1) void mlp128_bwd_ring_kernel(
 
 }  // namespace bwd
 }  // namespace nfx
-
-extern "C" int nfx_option_int(const char* name, int dflt);   // capi.cpp
 
 extern "C" {
 int nfx_launch_mlp128_bwd(int in_kind, const float* xyz, const float* xyz_dir, long long n, float xyz_scale,

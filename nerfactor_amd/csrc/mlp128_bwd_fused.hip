@@ -43,6 +43,7 @@
 #include "lds_dma.hpp"
 #include "mlp128_train_layout.hpp"
 #include "tr16.hpp"
+#include "launchers.hpp"
 
 namespace nfx {
 namespace bwd {

@@ -25,5 +25,21 @@ constexpr int kPreBiasFloats = 256;
 constexpr int kPreBytes = kPreWeightBytes + kPreBiasFloats * 4;
 // blob = [main] for NFX_IN_XYZ / NFX_IN_Z_RUSINK, [pre][main] for NFX_IN_XYZ_LDIR
 constexpr int kMaxZDim = 9;  // z0 rides in k-step 0, z1.. in k-step 1 (see brdf_input_slots)
+// B-operand slot table of the learned-BRDF input [z(z_dim) | posenc2(rusink)(15)], see brdf_spec_kernel in mlp128.hip:
+// [k-step][half][element] -> input row, -1 = zero.  Host side: the packers of capi_nerfactor.cpp and capi_train.cpp.
+inline void brdf_input_slots(int zd, int* slots /*[2][2][8]*/) {
+    for (int i = 0; i < 32; ++i) slots[i] = -1;
+    for (int h = 0; h < 2; ++h) {
+        int* s0 = slots + h * 8;
+        for (int j = 0; j < 6; ++j) s0[j] = zd + 3 + 6 * (j / 3) + (j % 3) + (h ? 3 : 0);
+        s0[6] = zd + (h ? 2 : 0);
+        s0[7] = h ? 0 : zd + 1;
+        int* s1 = slots + 16 + h * 8;
+        for (int j = 0; j < 8; ++j) {
+            const int i = 1 + 2 * j + h;
+            s1[j] = i < zd ? i : -1;
+        }
+    }
+}
 }  // namespace m128
 }  // namespace nfx

@@ -11,6 +11,7 @@
 #include "geom.hpp"
 #include "mlp128_layout.hpp"
 #include "mlp_x3.hpp"
+#include "launchers.hpp"
 
 namespace nfx {
 namespace x3m {

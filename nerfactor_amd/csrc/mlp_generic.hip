@@ -45,6 +45,7 @@
 #include "lds_dma.hpp"
 #include "mlp_generic.hpp"
 #include "tr16.hpp"
+#include "launchers.hpp"
 
 // This file is compiled three times (build time: one translation unit per operand mode, in parallel): as itself
 // (NFX_GENERIC_TU = 0: the bf16 instantiations, the mode-independent kernels and the C launch entry points) and through
@@ -945,14 +946,6 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(EmbedArgs a, const float
 // points of translation unit 0
 #define NFX_CAT_(a, b) a##b
 #define NFX_CAT(a, b) NFX_CAT_(a, b)
-extern "C" {
-int nfx_generic_fwd_m0(const nfx::generic::Args*, int, int, int, hipStream_t);
-int nfx_generic_fwd_m1(const nfx::generic::Args*, int, int, int, hipStream_t);
-int nfx_generic_fwd_m2(const nfx::generic::Args*, int, int, int, hipStream_t);
-int nfx_generic_bwd_m0(const nfx::generic::BwdArgs*, const nfx::generic::WgradArgs*, int, int, int, hipStream_t);
-int nfx_generic_bwd_m1(const nfx::generic::BwdArgs*, const nfx::generic::WgradArgs*, int, int, int, hipStream_t);
-int nfx_generic_bwd_m2(const nfx::generic::BwdArgs*, const nfx::generic::WgradArgs*, int, int, int, hipStream_t);
-}
 namespace {
 template <int M, int NW, bool WIDE = false>
 int launch_fwd(const nfx::generic::Args* args, int grid, int lds, hipStream_t st) {

@@ -13,6 +13,7 @@
 #include "rowsel.hpp"
 #include "lds_dma.hpp"
 #include "nerf_train_layout.hpp"
+#include "launchers.hpp"
 
 namespace nfx {
 namespace bwd {
@@ -471,8 +472,6 @@ int launch_scan(int* block_count, int n_blocks, int* count, hipStream_t st) {
 }
 }  // namespace rowsel
 }  // namespace nfx
-
-extern "C" int nfx_option_int(const char* name, int dflt);   // capi.cpp
 
 // the row-list workspace of nfx_launch_nerf_bwd (rowsel.hpp: count, block counts, n_pts indices)
 extern "C" size_t nfx_nerf_bwd_list_bytes(long long n_pts) { return nfx::rowsel::workspace_bytes(n_pts); }

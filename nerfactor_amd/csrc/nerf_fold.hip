@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "nerf_fold_layout.hpp"
+#include "launchers.hpp"
 
 namespace nfx {
 namespace nfold {

@@ -6,6 +6,7 @@
 #include "feat_store.hpp"
 #include "rowsel.hpp"
 #include "nerf_geom_layout.hpp"
+#include "launchers.hpp"
 
 namespace nfx {
 namespace geo {

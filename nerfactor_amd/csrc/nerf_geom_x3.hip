@@ -10,10 +10,7 @@
 #include "feat_store.hpp"
 #include "mlp_x3.hpp"
 #include "nerf_geom_layout.hpp"
-
-extern "C" int nfx_option_int(const char* name, int dflt);
-extern "C" int nfx_launch_nerf_sigma_x3_pipe(const float*, const float*, const float*, long long, int, const void*, float*,
-                                             const int*, const int*, int, int, int, hipStream_t);   // nerf_sigma_x3_pipe.hip
+#include "launchers.hpp"
 
 namespace nfx {
 namespace geo3 {

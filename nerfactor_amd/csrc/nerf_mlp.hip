@@ -4,6 +4,7 @@
 #include "mlp_engine.hpp"
 #include "nerf_layout.hpp"
 #include "nerf_fold_layout.hpp"
+#include "launchers.hpp"
 
 namespace nfx {
 

@@ -24,6 +24,7 @@
 #include "lds_dma.hpp"
 #include "nerf_layout.hpp"
 #include "nerf_fold_layout.hpp"
+#include "launchers.hpp"
 
 // NFX_V6_SIGMA (nerf_sigma_v6.hip includes this file with it defined): the DENSITY-ONLY form of the same dataflow over the
 // GEOM blob (nerf_geom_layout.hpp: chunks 0..63 = the encoder exactly as here, chunk 64 = the sigma tile, chunk 65 = the

@@ -7,6 +7,7 @@
 // the fp32 oracle: max |d rgb| <= 2e-4 (tests/test_gpu_nerf.py), the bound SURVEY.md §8d sets for an fp32 MFMA path.
 #include "mlp_x3.hpp"
 #include "nerf_layout.hpp"
+#include "launchers.hpp"
 
 namespace nfx {
 namespace x3 {

@@ -11,6 +11,7 @@
 #define NFX_V6_SIGMA 1
 #include "nerf_mlp_v6.hip"
 #include "nerf_geom_layout.hpp"
+#include "launchers.hpp"
 
 namespace nfx {
 namespace v6s {

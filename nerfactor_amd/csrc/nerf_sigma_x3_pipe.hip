@@ -20,6 +20,7 @@
 #include "mlp_x3.hpp"
 #include "lds_dma.hpp"
 #include "nerf_geom_layout.hpp"
+#include "launchers.hpp"
 
 namespace nfx {
 namespace geo3p {

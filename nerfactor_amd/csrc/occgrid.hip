@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "rowsel.hpp"
+#include "launchers.hpp"
 
 namespace nfx {
 namespace occ {

@@ -4,6 +4,7 @@
 // device->host copy, no host packer, no upload inside a training step (the map is built once per network by
 // nerfactor_amd/ops.py:DevicePacker from the host packer itself).
 #include "nfx_common.hpp"
+#include "launchers.hpp"
 
 namespace nfx {
 // One thread per 32-bit word of the blob; map[2i], map[2i+1]:

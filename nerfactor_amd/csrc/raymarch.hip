@@ -7,6 +7,7 @@
 // One wave (64 lanes) per ray for composite / sample_fine: the samples of a ray sit on the lanes,
 // loads are one contiguous 256-B / 1-KiB segment per wave, scans and reductions are wave shuffles.
 #include "nfx_common.hpp"
+#include "launchers.hpp"
 
 namespace nfx {
 

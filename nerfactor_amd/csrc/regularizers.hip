@@ -8,6 +8,7 @@
 //                       [H, W, 3] light probe (nerfactor.py:526-539) together with its gradient
 //                       2 w ((L - L[prev]) - (L[next] - L)) per axis — one block, fixed-order tree reduction (deterministic).
 #include <hip/hip_runtime.h>
+#include "launchers.hpp"
 
 namespace nfx {
 

@@ -1,6 +1,7 @@
 // selftest.hip — tiny diagnostic kernels that pin hardware conventions the fused kernels rely on.
 #include "nfx_common.hpp"
 #include "tr16.hpp"
+#include "launchers.hpp"
 
 namespace nfx {
 // D[32][32] = A[32][16] * B[16][32] with the documented lane maps of v_mfma_f32_32x32x16_bf16:

@@ -6,6 +6,7 @@
 // light positions, solid angles and all probes are staged once per workgroup in LDS.  Nothing of
 // size N x L x 3 is materialised; lvis[n, :] is read once (one coalesced row per point).
 #include "geom.hpp"
+#include "launchers.hpp"
 
 namespace nfx {
 

@@ -9,6 +9,7 @@
 #include <stdlib.h>
 
 #include "nfx_common.hpp"
+#include "launchers.hpp"
 
 namespace nfx {
 
@@ -520,17 +521,6 @@ int nfx_launch_amsgrad_dev(float* p, const float* g, float* m, float* v, float* 
                        vhat, n, lr_t_dev, b1, b2, eps);
     return (int)hipGetLastError();
 }
-// Host-side description of one GEMM of a batch (capi_train.cpp fills these).
-struct nfx_wgrad_call {
-    const void* xt;
-    const void* zt;
-    int k_in, n_out;
-    float* dw;
-    float* db;
-};
-
-int nfx_option_int(const char* key, int dflt);   // capi.cpp
-
 // blocks of 256 x 256 outputs the batch has when it takes the wide LDS form (wgrad_lds_kernel); 0: every GEMM is narrow
 static int wg_wide_blocks(const nfx_wgrad_call* calls, int n_calls) {
     bool all_narrow = nfx_option_int("wgrad_narrow", 1) != 0;
