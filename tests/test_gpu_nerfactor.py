@@ -107,8 +107,9 @@ def test_lvis_vs_oracle(nfx_lib, cuda, n, nl_h):
 def test_brdf_spec_vs_oracle(nfx_lib, cuda, nfx_opt, zd, variant, n, nl_h):
     """Learned-BRDF specular term: dense kernel (3), front-lit compaction with the reference's per-row op sequence
     (5) and with closed-form Rusinkiewicz angles (6, the default) against the oracle; point counts below / above the
-    number of waves of the grid (1024 / 2048), light counts that leave the last ballot half empty, and 800 lights — more
-    than the row queues of the default two-waves-per-SIMD form hold, so the one-wave-per-SIMD form runs."""
+    number of waves of the grid (1024: the default form, `brdf_compact_kernel<4, 1, 4>`, runs one wave per SIMD), light
+    counts that leave the last ballot half empty, and 800 lights — within the 832 that form's row queues and light table
+    hold, and more than the opt-in two-waves-per-SIMD form (`brdf_ct` 8) takes (576)."""
     from nerfactor_amd import ops
     nfx_opt.set("brdf_variant", variant)
     layers, out = net128(40 + zd, zd + 15, 1)
