@@ -274,6 +274,18 @@ NFX_API int nfx_brdf_spec_fwd(const float *dev_xyz, const float *dev_cam, const 
                       const float *dev_z, int z_dim, const float *dev_lxyz, int n_lights,
                       const void *dev_blob, int prec, int64_t n, float *dev_spec, void *stream);
 
+/* The BRDF prior rendered on spheres (brdf/renderer.py:167-181 over models/brdf.py:57-66), n_iden identities x n samples:
+ * rgb[b, i, c] = sum over the lights l with lweight[l, :] != 0 and local l.z > 0 of
+ *   softplus(out(mlp([z[b] | pe2(rusink(R_i l_i, R_i v_i))]))) * lweight[l, c] * (local l.z)
+ * R_i = gen_world2local(normal[i]), l_i = normalize(lxyz[l] - xyz[i]), v_i = normalize(cam - xyz[i]);
+ * lweight = light * area.  blob: nfx_mlp128_pack_weights(NFX_IN_Z_RUSINK, bf16).  n_lights % 32 == 0, <= 1024; z_dim 1..8.
+ * cam3: three floats on the HOST.  Every row is the row of nfx_brdf_spec_fwd (same bits); a pixel is the fp32 sum of its
+ * lights in ascending order, independent of the rest of the launch.  No workspace, no atomics.                         */
+NFX_API int nfx_brdf_sphere_fwd(const float *dev_xyz, const float *dev_normal, int64_t n, const float *cam3,
+                                const float *dev_z, int z_dim, int n_iden, const float *dev_lxyz,
+                                const float *dev_lweight, int n_lights, const void *dev_blob,
+                                float *dev_rgb /* [n_iden, n, 3] */, void *stream);
+
 /* Rusinkiewicz coordinates (phi_d, theta_h, theta_d), util/geom.py:152-192. a,b [n,3]. */
 NFX_API int nfx_dir2rusink(const float *dev_a, const float *dev_b, int64_t n, float *dev_rusink,
                    void *stream);

@@ -41,7 +41,7 @@ VGPR_FORM = ['-mllvm', '-amdgpu-mfma-vgpr-form']
 FAST_DIV = ['-fno-hip-fp32-correctly-rounded-divide-sqrt']
 # nerf_mlp.hip: the folded 4 x 64 kernel (fold::nerf_mlp_bf16_kernel<2, 4>) spills 5 dwords to scratch memory without it although
 # it needs 120 registers fewer than the unfolded one; with it no kernel of the file but the rolled experiment uses scratch
-PER_FILE_FLAGS = {'lvis_v2.hip': VGPR_FORM, 'nerf_mlp.hip': VGPR_FORM, 'nerf_mlp_v6.hip': VGPR_FORM, 'nerf_sigma_v6.hip': VGPR_FORM,
+PER_FILE_FLAGS = {'lvis_v2.hip': VGPR_FORM, 'brdf_sphere.hip': VGPR_FORM, 'nerf_mlp.hip': VGPR_FORM, 'nerf_mlp_v6.hip': VGPR_FORM, 'nerf_sigma_v6.hip': VGPR_FORM,
                   'nerf_sigma_x3_pipe.hip': VGPR_FORM,
                   'nerf_geom.hip': VGPR_FORM, 'mlp128_bwd_fused.hip': VGPR_FORM, 'shade.hip': FAST_DIV}
 

@@ -258,6 +258,22 @@ int nfx_brdf_spec_fwd(const float* xyz, const float* cam, const float* normal, c
                           "brdf_spec_fwd");
 }
 
+// ------------------------------------------------------------------------------ the prior on spheres (brdf_sphere.hip)
+int nfx_brdf_sphere_fwd(const float* xyz, const float* normal, int64_t n, const float* cam3, const float* z, int z_dim,
+                        int n_iden, const float* lxyz, const float* lweight, int n_lights, const void* blob, float* rgb,
+                        void* stream) {
+    REQUIRE(n >= 0 && n_iden >= 0, "nfx_brdf_sphere_fwd: n (%lld) or n_iden (%d) < 0", (long long)n, n_iden);
+    REQUIRE(z_dim >= 1 && z_dim <= 8, "nfx_brdf_sphere_fwd: z_dim %d not in [1, 8]", z_dim);
+    REQUIRE(n_lights > 0 && n_lights % 32 == 0 && n_lights <= 1024,
+            "nfx_brdf_sphere_fwd: n_lights (%d) must be a multiple of 32 in [32, 1024]", n_lights);
+    if (n == 0 || n_iden == 0) return NFX_OK;
+    REQUIRE(xyz && normal && cam3 && z && lxyz && lweight && blob && rgb, "nfx_brdf_sphere_fwd: null pointer");
+    if (!ALIGNED(blob, 16)) return nfx_fail(NFX_EALIGN, "nfx_brdf_sphere_fwd: blob must be 16-byte aligned");
+    return nfx_hip_result(nfx_launch_brdf_sphere(xyz, normal, n, cam3, z, z_dim, n_iden, lxyz, lweight, n_lights, blob, rgb,
+                                                 nfx_option_int("m128_blocks", 256), (hipStream_t)stream),
+                          "brdf_sphere_fwd");
+}
+
 // ------------------------------------------------------------------------------ shading
 static int check_shade(const char* who, const float* xyz, const float* cam, const float* normal,
                        const float* albedo, const float* rough, const float* spec, const float* lvis,

@@ -33,6 +33,10 @@ int nfx_launch_brdf_rows(int bwd, const float* z, int z_dim, const float* rusink
                          const float* dout, float* out_or_dz, void* wsp, long long ld, int max_blocks, hipStream_t st);
 // ---- brdf_rows_geom.hip
 int nfx_launch_brdf_rows_geom(const nfx::rowsgeom::Args* a, int bwd, hipStream_t st);
+// ---- brdf_sphere.hip
+int nfx_launch_brdf_sphere(const float* xyz, const float* normal, long long n, const float* cam3, const float* z, int z_dim, int n_iden,
+                           const float* lxyz, const float* lweight, int n_lights, const void* blob, float* rgb, int max_blocks,
+                           hipStream_t st);
 // ---- loss.hip
 int nfx_launch_pair_loss(int bwd, const nfx_loss_term* terms, int n_terms, const float* alpha, float bg, long long n, float* loss,
                          const float* dloss, hipStream_t st);

@@ -11,6 +11,21 @@ import numpy as np
 from .base import Dataset as BaseDataset
 
 
+def split_test_identities(brdf_names, seed=0, n_iden=20, n_between=11):
+    """The ids of the test split: the seen materials (novel coordinates, seen identities), then the seeded walk between
+    `n_iden` of them, `n_between` steps per leg: '<n>_<w1>_<mat1>_<w2>_<mat2>' (brdf_merl.py:45-62).  Shared by the data set
+    and by explore_brdf_space, which needs the ids but no test coordinates."""
+    ids = list(brdf_names)
+    rng = np.random.RandomState(seed)
+    mats = rng.choice(brdf_names, min(n_iden, len(brdf_names)), replace=False)
+    k = 0
+    for a_i in range(len(mats) - 1):
+        for a in np.linspace(1, 0, n_between, endpoint=True):
+            ids.append('%06d_%f_%s_%f_%s' % (k, a, mats[a_i], 1 - a, mats[a_i + 1]))
+            k += 1
+    return ids
+
+
 class Dataset(BaseDataset):
     keep_order = True   # test ids: seen materials first, then the interpolation sequence
 
@@ -26,14 +41,7 @@ class Dataset(BaseDataset):
             if len(test_paths) != 1:
                 raise ValueError("There should be a single set of test coordinates, shared by all identities")
             self.test_data = dict(np.load(test_paths[0], allow_pickle=True))
-            test_ids += self.brdf_names                           # novel coordinates, seen identities
-            rng = np.random.RandomState(seed)                     # then interpolated identities
-            mats = rng.choice(self.brdf_names, min(n_iden, len(self.brdf_names)), replace=False)
-            k = 0
-            for a_i in range(len(mats) - 1):
-                for a in np.linspace(1, 0, n_between, endpoint=True):
-                    test_ids.append('%06d_%f_%s_%f_%s' % (k, a, mats[a_i], 1 - a, mats[a_i + 1]))
-                    k += 1
+            test_ids += split_test_identities(self.brdf_names, seed=seed, n_iden=n_iden, n_between=n_between)
         self.paths = {'train': train_paths, 'vali': vali_paths, 'test': test_ids}
         super().__init__(config, mode, debug=debug, device=device)
 

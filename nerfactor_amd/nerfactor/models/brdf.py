@@ -5,6 +5,7 @@ weights, the latent codes and the config surface, and trains on the same fused t
 from os.path import basename
 import glob
 
+import numpy as np
 import torch
 
 from ... import autograd as nfx_grad, ops
@@ -139,6 +140,14 @@ class Model(BaseModel):
         to_vis.update(pred)
         return pred, gt, {}, to_vis
 
+    def z_of_id(self, id_):
+        """[1, z_dim] latent code of a test id: a seen material's own, or the interpolation '<n>_<w1>_<mat1>_<w2>_<mat2>' names."""
+        if id_ in self.brdf_names:
+            return self.latent_code(self.brdf_names.index(id_)).reshape(1, -1)
+        _, w1, rest = id_.split('_', 2)
+        mat1, w2, mat2 = self._split_interp_id(rest)
+        return self.latent_code.interp(float(w1), self.brdf_names.index(mat1), float(w2), self.brdf_names.index(mat2)).reshape(1, -1)
+
     def _split_interp_id(self, rest):
         """'<mat1>_<w2>_<mat2>' -> (mat1, w2, mat2) with material names that may themselves contain '_'."""
         for name in sorted(self.brdf_names, key=len, reverse=True):
@@ -163,8 +172,96 @@ class Model(BaseModel):
             loss = loss + weight * fn(f(gt['brdf']), f(pred['brdf_reci']), **kwargs)
         return loss
 
+    # ------------------------------------------------------------------ looking at the prior (brdf.py:194-215, explore_brdf_space.py)
+    def _sphere_scene(self, envmap, envmap_inten, envmap_h, ims, spp, device):
+        """The host scene (brdf/renderer.py:SphereRenderer) and its device tensors, cached per (envmap, inten, h, ims, spp)."""
+        from ...brdf.renderer import SphereRenderer
+        key = (str(envmap), float(envmap_inten), None if envmap_h is None else int(envmap_h), int(ims), int(spp), str(device))
+        scenes = self.__dict__.setdefault('_sphere_scenes', {})
+        if key not in scenes:
+            r = SphereRenderer(envmap, envmap_inten=envmap_inten, envmap_h=envmap_h, ims=ims, spp=spp)
+            dev = lambda a: torch.as_tensor(a, dtype=torch.float32, device=device).contiguous()
+            fg = r.is_fg.reshape(-1)
+            lweight = r.light.reshape(-1, 3) * r.lareas.reshape(-1, 1)
+            scenes[key] = {
+                'renderer': r, 'fg': torch.as_tensor(fg, device=device), 'xyz': dev(r.xyz.reshape(-1, 3)[fg]),
+                'normal': dev(r.normal.reshape(-1, 3)[fg]), 'lxyz': dev(r.lxyz.reshape(-1, 3)), 'lweight': dev(lweight)}
+        return scenes[key]
+
+    def _sphere_rows(self, scene):
+        """The explicit rows of a scene: (sample index [M], weight * cos [M, 3], rusink [M, 3]) of the front-lit (sample,
+        light) pairs whose light is not dark, Rusinkiewicz angles by nfx_dir2rusink on the scene's local directions."""
+        if 'rows' not in scene:
+            r, dev = scene['renderer'], scene['xyz'].device
+            fg = r.is_fg.reshape(-1)
+            lit = (r.light.reshape(-1, 3) != 0).any(1)
+            sel = (r.lvis.reshape(fg.size, -1)[fg] > 0) & lit[None, :]
+            si, li = np.nonzero(sel)
+            ldir = r.ldir.reshape(fg.size, -1, 3)[fg][si, li]
+            vdir = r.vdir.reshape(fg.size, 3)[fg][si]
+            f32 = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32, device=dev)
+            rusink = ops.dir2rusink(f32(ldir), f32(vdir)) if si.size else torch.zeros((0, 3), device=dev)
+            scene['rows'] = (torch.as_tensor(si, device=dev), f32(r.lcontrib.reshape(fg.size, -1, 3)[fg][si, li]), rusink)
+        return scene['rows']
+
+    def render_spheres(self, z, envmap='point', envmap_inten=40., envmap_h=16, ims=128, spp=1, white_bg=True):
+        """[B, ims, ims, 3] device tensor: a sphere of each latent code z[B, z_dim] under a light probe (the reference's
+        render.png, brdf.py:209-215, for B identities at once).  The shipped architecture renders its foreground samples in
+        one fused launch (nfx_brdf_sphere_fwd: rows, cosine weighting and the sum over lights in the kernel); any other
+        shape evaluates the explicit front-lit rows through _eval_brdf_at and sums them per image."""
+        with torch.no_grad():
+            z = z.detach().float().reshape(-1, self.z_dim).contiguous()
+            scene = self._sphere_scene(envmap, envmap_inten, envmap_h, ims, spp, z.device)
+            r, n_fg = scene['renderer'], scene['xyz'].shape[0]
+            if self.tuned and self.z_dim <= 8 and scene['lxyz'].shape[0] % 32 == 0 and scene['lxyz'].shape[0] <= 1024:
+                ks, bs = self.net['brdf_mlp'].kernels_and_biases()
+                ko, bo = self.net['brdf_out'].kernels_and_biases()
+                from ... import _capi
+                blob = self._packed('brdf_sphere', ks + ko + bs + bo,
+                                    lambda k, b: ops.pack_mlp128_weights(k, b, _capi.IN_Z_RUSINK, 1, z_dim=self.z_dim))
+                fg_rgb = ops.brdf_sphere_fwd(scene['xyz'], scene['normal'], r.cam_loc, z, scene['lxyz'], scene['lweight'], blob)
+            else:
+                si, wcos, rusink = self._sphere_rows(scene)
+                fg_rgb = torch.zeros((z.shape[0], n_fg, 3), device=z.device)
+                for b in range(z.shape[0]):
+                    if si.numel():
+                        brdf, _ = self._eval_brdf_at(z[b:b + 1].expand(si.numel(), -1), rusink)
+                        fg_rgb[b].index_add_(0, si, brdf.reshape(-1, 1) * wcos)
+            res = r.ims * r.sps
+            img = torch.full((z.shape[0], res * res, 3), 1. if white_bg else 0., device=z.device)
+            img[:, scene['fg']] = fg_rgb
+            return img.reshape(z.shape[0], r.ims, r.sps, r.ims, r.sps, 3).sum(dim=(2, 4)) / float(r.sps ** 2)
+
+    def characteristic_slices(self, z):
+        """[B, 90, 90]: the prior of each latent code on the MERL characteristic slice (phi_d = 90 degrees; merl.py:78-96)."""
+        from ...brdf import merl
+        with torch.no_grad():
+            z = z.detach().float().reshape(-1, self.z_dim)
+            coords = torch.as_tensor(merl.characteristic_slice_rusink().reshape(-1, 3).copy(), dtype=torch.float32, device=z.device)
+            m = coords.shape[0]
+            brdf, _ = self._eval_brdf_at(z[:, None, :].expand(-1, m, -1).reshape(-1, self.z_dim), coords.repeat(z.shape[0], 1))
+            return brdf.reshape(z.shape[0], 90, 90)
+
+    @staticmethod
+    def write_sphere_vis(outdir, id_, z, cslice, render):
+        """metadata.json, cslice.png and render.png of one identity (cslice [90, 90] reflectances, render [ims, ims, 3])."""
+        import json
+        import os
+        import numpy as np
+        from PIL import Image
+        from ...brdf import merl
+        os.makedirs(outdir, exist_ok=True)
+        to_np = lambda a: a.detach().float().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        Image.fromarray(merl.characteristic_slice_as_img(to_np(cslice))).save(os.path.join(outdir, 'cslice.png'))
+        u8 = (np.clip(to_np(render), 0, 1) * 255).astype(np.uint8)       # write_arr(clip=True)
+        Image.fromarray(u8).save(os.path.join(outdir, 'render.png'))
+        with open(os.path.join(outdir, 'metadata.json'), 'w') as h:   # last: the files of a finished batch are all there
+            json.dump({'id': id_, 'z': [float(v) for v in to_np(z).reshape(-1)]}, h, indent=4, sort_keys=True)
+
     def vis_batch(self, data_dict, outdir, mode='train', dump_raw_to=None, **kwargs):
-        """Raw dump only (the reference renders the BRDF on spheres here, brdf.py:138-220: viewer tooling)."""
+        """The raw dump; in 'test' mode also metadata.json, cslice.png (the first 90 x 90 rows of data_dict['brdf'], as the
+        reference's test set orders them) and render.png (the identity on a sphere under the 'point' probe) — brdf.py:157-215
+        without the bar plots."""
         import os
         import numpy as np
         self._validate_mode(mode)
@@ -178,3 +275,13 @@ class Model(BaseModel):
             np.savez(h, **arrays)
         if mode != 'train':
             os.makedirs(outdir, exist_ok=True)
+        if mode == 'test':
+            id_ = data_dict['id'][0]
+            id_ = id_.decode() if isinstance(id_, bytes) else str(id_)
+            z = data_dict['z'][:1]
+            if data_dict['brdf'].shape[0] < 90 * 90 or any(data_dict.get(k) is None for k in ('envmap_h', 'ims', 'spp')):
+                raise ValueError("vis_batch(mode='test') needs a batch of the test split: the characteristic slice's 90 x 90 rows "
+                                 "first, and envmap_h / ims / spp (got %d rows)" % data_dict['brdf'].shape[0])
+            envmap_h, ims, spp = (int(data_dict[k][0]) for k in ('envmap_h', 'ims', 'spp'))
+            render = self.render_spheres(z, 'point', 40., envmap_h, ims, spp)[0]
+            self.write_sphere_vis(outdir, id_, z, data_dict['brdf'][:90 * 90].reshape(90, 90), render)

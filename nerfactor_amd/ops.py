@@ -732,6 +732,28 @@ def brdf_spec_fwd(xyz, cam, normal, z, lxyz, blob, prec='bf16'):
     return out
 
 
+def brdf_sphere_fwd(xyz, normal, cam, z, lxyz, lweight, blob, out=None):
+    """rgb[B, n, 3]: the BRDF prior of B latent codes z[B, z_dim] rendered at n sphere samples (xyz, normal [n, 3]) seen from
+    `cam` (three numbers) under the lights lxyz[L, 3] with lweight[L, 3] = light * area: the sum over the lit front-facing
+    lights of brdf * lweight * cos, accumulated in the kernel (nfx_brdf_sphere_fwd).  blob: pack_mlp128_weights(IN_Z_RUSINK).
+    Every element of the result is written (`out`: a buffer to write into instead of a new one)."""
+    xyz = _dev(xyz, 'xyz', (None, 3))
+    n = xyz.shape[0]
+    normal = _dev(normal, 'normal', (n, 3))
+    z = _dev(z, 'z', (None, None))
+    lxyz = _dev(lxyz, 'lxyz', (None, 3))
+    nl = lxyz.shape[0]
+    lweight = _dev(lweight, 'lweight', (nl, 3))
+    cam3 = (ctypes.c_float * 3)(*[float(v) for v in (cam.tolist() if hasattr(cam, 'tolist') else cam)])
+    if out is None:
+        out = torch.empty((z.shape[0], n, 3), dtype=torch.float32, device=xyz.device)
+    elif not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (z.shape[0], n, 3):
+        raise _capi.NfxError("brdf_sphere_fwd: `out` must be a contiguous CUDA float32 [%d, %d, 3] tensor" % (z.shape[0], n))
+    check(lib.nfx_brdf_sphere_fwd(_ptr(xyz), _ptr(normal), n, ctypes.cast(cam3, ctypes.c_void_p), _ptr(z), z.shape[1], z.shape[0],
+                                  _ptr(lxyz), _ptr(lweight), nl, _ptr(blob), _ptr(out), _stream()), 'nfx_brdf_sphere_fwd')
+    return out
+
+
 def _shade_common(xyz, cam, normal, albedo, rough, spec, lvis, lxyz, lareas, lvis_row=None):
     xyz = _dev(xyz, 'xyz', (None, 3))
     n = xyz.shape[0]
