@@ -1,5 +1,5 @@
-"""Inputs and oracles for the NeRF point kernels (nerf_mlp_v6.hip, nerf_mlp.hip, nerf_mlp_x3.hip, nerf_sigma_v6.hip,
-nerf_geom.hip, nerf_geom_x3.hip, nerf_sigma_x3_pipe.hip): no GPU here.
+"""Inputs and oracles for the NeRF point kernels (nerf_mlp_v6.hip and nerf_sigma_v6.hip on nerf_v6_engine.hpp, nerf_mlp.hip,
+nerf_mlp_x3.hip, nerf_geom.hip, nerf_geom_x3.hip, nerf_sigma_x3_pipe.hip): no GPU here.
 
 Every one of these kernels gives a lane the flat point index m, reads z[m] and finds the ray with ray = m / n_samples.  What
 the older shapes cannot do, these inputs do:
@@ -23,12 +23,18 @@ from tests import common
 # ---------------------------------------------------------------------------------------------- constants of the kernels
 # (name of the source, pattern that must be found in it): test_cpu_nerf_point_cases.py
 SOURCE_CONSTANTS = [
-    ('nerf_mlp_v6.hip', r'constexpr int kNW = 4, kCT = 2;'),
-    ('nerf_mlp_v6.hip', r'constexpr int kTilePts = kNW \* 32 \* kCT;'),
+    # nerf_v6_engine.hpp: the tile of the render kernels (nerf_mlp_v6.hip) and of the density kernels (nerf_sigma_v6.hip), once
+    ('nerf_v6_engine.hpp', r'constexpr int kNW = 4, kCT = 2;'),
+    ('nerf_v6_engine.hpp', r'constexpr int kTilePts = kNW \* 32 \* kCT;'),
     ('nerf_mlp_v6.hip', r'm\[c\] = tl \* kTilePts \+ wave \* \(32 \* kCT\) \+ c \* 32 \+ p;'),
     ('nerf_mlp_v6.hip', r'const long long mm = m\[c\] < n_pts \? m\[c\] : n_pts - 1;\s*const long long ray = mm / n_samples;'),
-    ('nerf_sigma_v6.hip', r'constexpr int kTilePts = kNW \* 32 \* kCT;'),
-    ('nerf_sigma_v6.hip', r'const long long mm = m\[c\] < n_pts \? m\[c\] : n_pts - 1;\s*const long long ray = mm / n_samples;'),
+    # the one density body: position m -> sample src(m) -> ray; every sample is src(m) = m, a listed one src(m) = list[m]
+    ('nerf_sigma_v6.hip', r'const long long m = tl \* kTilePts \+ wave \* \(32 \* kCT\) \+ c \* 32 \+ p;'),
+    ('nerf_sigma_v6.hip', r'const long long mm = src\(m < n_pts \? m : n_pts - 1\);\s*const long long ray = mm / n_samples;'),
+    ('nerf_sigma_v6.hip', r'struct EverySample \{[^}]*operator\(\)\(long long m\) const \{ return m; \}'),
+    ('nerf_sigma_v6.hip', r'struct ListedSample \{[^}]*operator\(\)\(long long m\) const \{ return list\[m\]; \}'),
+    ('nerf_sigma_v6.hip', r'nerf_sigma_v6_body\(rayo, rayd, zbuf, n_pts, n_samples, blob, out, EverySample\{\}\);'),
+    ('nerf_sigma_v6.hip', r'nerf_sigma_v6_body\(rayo, rayd, zbuf, n_pts, n_samples, blob, out, ListedSample\{list\}\);'),
     ('nerf_mlp.hip', r'return launch_variant<2, 4>\('),
     ('nerf_mlp.hip', r'return launch_variant<1, 8>\('),
     ('nerf_mlp.hip', r'return launch_variant<2, 4, true>\('),
@@ -48,7 +54,7 @@ SOURCE_CONSTANTS = [
 ]
 WAVE = 64                     # points of a wave of the 4 x 64 kernels: two column tiles of 32
 COL_TILE = 32
-TILE = 4 * 32 * 2             # nerf_mlp_v6.hip, nerf_sigma_v6.hip, nerf_mlp.hip <2, 4> and <1, 8>, nerf_sigma_geo_kernel (8 x 32)
+TILE = 4 * 32 * 2             # nerf_v6_engine.hpp (nerf_mlp_v6.hip, nerf_sigma_v6.hip), nerf_mlp.hip <2, 4> and <1, 8>, nerf_sigma_geo_kernel (8 x 32)
 TILE_X3 = 4 * 32              # nerf_mlp_x3.hip, nerf_geom.hip, nerf_geom_x3.hip, nerf_sigma_x3_pipe.hip
 DEFAULT_BLOCKS = 256
 

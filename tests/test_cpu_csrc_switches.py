@@ -9,7 +9,6 @@ import re
 from tests.conftest import ROOT
 
 ALLOWED = {
-    'NFX_V6_SIGMA',     # nerf_mlp_v6.hip included by nerf_sigma_v6.hip
     'NFX_GENERIC_TU',   # mlp_generic.hip included by mlp_generic_{x3,native}.hip
     'NFX_H_',           # include guard of include/nfx.h
     '__cplusplus',

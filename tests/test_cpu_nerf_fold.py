@@ -1,4 +1,5 @@
-"""The bottleneck fold of the NeRF render path, without a GPU (csrc/nerf_fold.hip, nerf_fold_layout.hpp, nerf_mlp_v6.hip).
+"""The bottleneck fold of the NeRF render path, without a GPU (csrc/nerf_fold.hip, nerf_fold_layout.hpp, nerf_mlp_v6.hip,
+nerf_v6_engine.hpp).
 
 The network's bottleneck layer has no activation and feeds rgb_out[0] only, so the render kernels multiply enc[7]'s output
 by W' = Wb W0a directly and skip the bottleneck's 8 tiles.  Checked here: the arithmetic against the oracle, the fragment-
@@ -166,11 +167,18 @@ def test_the_restated_model_agrees_with_the_original_and_catches_bad_maps():
 
 
 def test_ring_model_matches_the_kernel_constants():
-    src = open(os.path.join(CSRC, 'nerf_mlp_v6.hip')).read()
-    assert 'template <int DMA, bool FOLD = false> constexpr int ring_of = DMA == 1 ? 6 : FOLD ? 4 : 3;' in src
-    assert 'return DMA == 1 ? (k < 66 ? k % 6 : k - 65) : (k == 69 ? 3 : k % 3);' in src
+    src = open(os.path.join(CSRC, 'nerf_v6_engine.hpp')).read()
+    assert 'enum class Seq { Packed, Render, Geom };' in src
+    assert 'template <int DMA, Seq S> constexpr int ring_of = DMA == 1 ? 6 : S == Seq::Render ? 4 : 3;' in src
+    # the folded maps belong to the render sequence alone; the packed and the GEOM sequence use k % ring
+    assert re.search(r'constexpr int slot_of\(int k\) \{\s*if \(S != Seq::Render\) return k % ring_of<DMA, S>;\s*'
+                     r'return DMA == 1 \? \(k < 66 \? k % 6 : k - 65\) : \(k == 69 \? 3 : k % 3\);\s*\}', src)
     assert re.search(r'template <int DMA> constexpr int dist_of = DMA == 1 \? kDmaDist : DMA \? 3 : 2;', src)
     assert 'constexpr int kDmaDist = 3;' in src
+    assert ('template <Seq S> constexpr int n_chunks = S == Seq::Render ? nerf::fold::kNChunks : S == Seq::Geom ? 66 : '
+            'nerf::kNChunks;') in src
     lay = open(os.path.join(CSRC, 'nerf_fold_layout.hpp')).read()
     assert 'constexpr int kNChunks = 70;' in lay
+    assert 'constexpr int kNChunks = 78;' in open(os.path.join(CSRC, 'nerf_layout.hpp')).read()
+    assert '#if' not in src and '.hip"' not in open(os.path.join(CSRC, 'nerf_sigma_v6.hip')).read()
     assert max(slot_dma(k) for k in range(70)) == 5 and max(slot_staged(k) for k in range(70)) == 3
