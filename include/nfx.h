@@ -286,6 +286,29 @@ NFX_API int nfx_brdf_sphere_fwd(const float *dev_xyz, const float *dev_normal, i
                                 const float *dev_lweight, int n_lights, const void *dev_blob,
                                 float *dev_rgb /* [n_iden, n, 3] */, void *stream);
 
+/* Measured MERL BRDFs (brdf/merl/merl.py:MERL.query).  table4: float32 [180 * 90 * 90, 4] in cube order (phi_d, theta_h,
+ * theta_d), rgb plus one pad float, every INVALID entry -1 in all four lanes; 16-byte aligned; at least one valid entry
+ * (the host checks).  For each query rusink[i] = (phi_d, theta_h, theta_d) in radians: idx[i] = the flat cube index of the
+ * VALID entry nearest in Euclidean distance over the raw angles (the reference's k-d tree; grid coordinates of
+ * merl_to_rusink in fp32; ties go to the smaller index), rgb[i] = that entry's three floats, bit for bit.  Coordinates
+ * outside the cube's range are legal; a non-finite one gives idx -1 and rgb NaN.  dev_idx (int32 [n]) may be NULL.
+ * The search is exact for any table; a row depends on its own query and on nothing else in the launch.               */
+NFX_API int nfx_merl_query(const void *dev_table4, const float *dev_rusink, int64_t n, float *dev_rgb,
+                           int *dev_idx, void *stream);
+
+/* A measured BRDF rendered on a sphere (data_gen/merl/make_dataset.py:129-138 over brdf/renderer.py:167-181), n samples:
+ * rgb[i, c] = sum over the lights l with lweight[l, :] != 0 and local l.z > 0 of
+ *   table4[idx(i, l), c] * lweight[l, c] * (local l.z),   idx(i, l) = the lookup of nfx_merl_query at
+ *   brdf.merl.dir2rusink(R_i l_i, R_i v_i), theta_h and theta_d as atan2 of their sine and cosine;
+ * R_i = gen_world2local(normal[i]), l_i = normalize(lxyz[l] - xyz[i]), v_i = normalize(cam - xyz[i]); lweight = light * area.
+ * n_lights % 32 == 0, <= 1024.  cam3: three floats on the HOST.  dev_idx (int32 [n, n_lights]) may be NULL; otherwise it
+ * receives the chosen entry of every row and -1 for the rows that do not contribute.  A pixel is the fp32 sum of its
+ * lights, tiles of 64 in ascending order, independent of the rest of the launch; a sample without a lit front-facing
+ * light stores 0.  No workspace, no atomics.                                                                          */
+NFX_API int nfx_merl_sphere_fwd(const float *dev_xyz, const float *dev_normal, int64_t n, const float *cam3,
+                                const void *dev_table4, const float *dev_lxyz, const float *dev_lweight,
+                                int n_lights, float *dev_rgb /* [n, 3] */, int *dev_idx, void *stream);
+
 /* Rusinkiewicz coordinates (phi_d, theta_h, theta_d), util/geom.py:152-192. a,b [n,3]. */
 NFX_API int nfx_dir2rusink(const float *dev_a, const float *dev_b, int64_t n, float *dev_rusink,
                    void *stream);

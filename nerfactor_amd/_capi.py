@@ -62,6 +62,8 @@ SIGNATURES = {
                                 _p]),
     'nfx_brdf_spec_fwd': (_i, [_p, _p, _p, _p, _i, _p, _i, _p, _i, _i64, _p, _p]),
     'nfx_brdf_sphere_fwd': (_i, [_p, _p, _i64, _p, _p, _i, _i, _p, _p, _i, _p, _p, _p]),
+    'nfx_merl_query': (_i, [_p, _p, _i64, _p, _p, _p]),
+    'nfx_merl_sphere_fwd': (_i, [_p, _p, _i64, _p, _p, _p, _p, _i, _p, _p, _p]),
     'nfx_dir2rusink': (_i, [_p, _p, _i64, _p, _p]),
     'nfx_mlp128_train_packed_bytes': (_sz, [_i]),
     'nfx_mlp128_pack_train_weights': (_i, [_pp, _pp, _i, _i, _i, _p, _sz]),

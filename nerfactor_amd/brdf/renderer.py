@@ -143,3 +143,28 @@ class SphereRenderer:
         render[~self.is_fg] = 1. if white_bg else 0.
         s = self.sps
         return render.reshape(self.ims, s, self.ims, s, 3).sum(axis=(1, 3)) / (s ** 2)
+
+    def device_scene(self, device):
+        """What the fused sphere kernels (nfx_brdf_sphere_fwd, nfx_merl_sphere_fwd) take of this scene, as float32 tensors on
+        `device`, built once per device: the foreground samples' xyz and normal, lxyz, lweight = light * area, the
+        foreground mask 'fg' over the flattened sample grid, and 'renderer' (this object)."""
+        import torch
+        scenes = self.__dict__.setdefault('_device_scenes', {})
+        key = str(device)
+        if key not in scenes:
+            dev = lambda a: torch.as_tensor(a, dtype=torch.float32, device=device).contiguous()
+            fg = self.is_fg.reshape(-1)
+            lweight = self.light.reshape(-1, 3) * self.lareas.reshape(-1, 1)
+            scenes[key] = {
+                'renderer': self, 'fg': torch.as_tensor(fg, device=device), 'xyz': dev(self.xyz.reshape(-1, 3)[fg]),
+                'normal': dev(self.normal.reshape(-1, 3)[fg]), 'lxyz': dev(self.lxyz.reshape(-1, 3)), 'lweight': dev(lweight)}
+        return scenes[key]
+
+    def assemble(self, fg_rgb, white_bg=True):
+        """fg_rgb [B, n_fg, 3] device tensor of the foreground samples -> [B, ims, ims, 3]: background, mean over a pixel's samples."""
+        import torch
+        res = self.ims * self.sps
+        fg = self.device_scene(fg_rgb.device)['fg']
+        img = torch.full((fg_rgb.shape[0], res * res, 3), 1. if white_bg else 0., device=fg_rgb.device)
+        img[:, fg] = fg_rgb
+        return img.reshape(fg_rgb.shape[0], self.ims, self.sps, self.ims, self.sps, 3).sum(dim=(2, 4)) / float(self.sps ** 2)

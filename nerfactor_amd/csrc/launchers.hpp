@@ -37,6 +37,10 @@ int nfx_launch_brdf_rows_geom(const nfx::rowsgeom::Args* a, int bwd, hipStream_t
 int nfx_launch_brdf_sphere(const float* xyz, const float* normal, long long n, const float* cam3, const float* z, int z_dim, int n_iden,
                            const float* lxyz, const float* lweight, int n_lights, const void* blob, float* rgb, int max_blocks,
                            hipStream_t st);
+// ---- merl.hip
+int nfx_launch_merl_query(const void* table4, const float* rusink, long long n, float* rgb, int* idx, hipStream_t st);
+int nfx_launch_merl_sphere(const float* xyz, const float* normal, long long n, const float* cam3, const void* table4, const float* lxyz,
+                           const float* lweight, int n_lights, float* rgb, int* idx, hipStream_t st);
 // ---- loss.hip
 int nfx_launch_pair_loss(int bwd, const nfx_loss_term* terms, int n_terms, const float* alpha, float bg, long long n, float* loss,
                          const float* dloss, hipStream_t st);

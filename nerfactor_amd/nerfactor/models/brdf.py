@@ -179,13 +179,7 @@ class Model(BaseModel):
         key = (str(envmap), float(envmap_inten), None if envmap_h is None else int(envmap_h), int(ims), int(spp), str(device))
         scenes = self.__dict__.setdefault('_sphere_scenes', {})
         if key not in scenes:
-            r = SphereRenderer(envmap, envmap_inten=envmap_inten, envmap_h=envmap_h, ims=ims, spp=spp)
-            dev = lambda a: torch.as_tensor(a, dtype=torch.float32, device=device).contiguous()
-            fg = r.is_fg.reshape(-1)
-            lweight = r.light.reshape(-1, 3) * r.lareas.reshape(-1, 1)
-            scenes[key] = {
-                'renderer': r, 'fg': torch.as_tensor(fg, device=device), 'xyz': dev(r.xyz.reshape(-1, 3)[fg]),
-                'normal': dev(r.normal.reshape(-1, 3)[fg]), 'lxyz': dev(r.lxyz.reshape(-1, 3)), 'lweight': dev(lweight)}
+            scenes[key] = SphereRenderer(envmap, envmap_inten=envmap_inten, envmap_h=envmap_h, ims=ims, spp=spp).device_scene(device)
         return scenes[key]
 
     def _sphere_rows(self, scene):
@@ -227,10 +221,7 @@ class Model(BaseModel):
                     if si.numel():
                         brdf, _ = self._eval_brdf_at(z[b:b + 1].expand(si.numel(), -1), rusink)
                         fg_rgb[b].index_add_(0, si, brdf.reshape(-1, 1) * wcos)
-            res = r.ims * r.sps
-            img = torch.full((z.shape[0], res * res, 3), 1. if white_bg else 0., device=z.device)
-            img[:, scene['fg']] = fg_rgb
-            return img.reshape(z.shape[0], r.ims, r.sps, r.ims, r.sps, 3).sum(dim=(2, 4)) / float(r.sps ** 2)
+            return r.assemble(fg_rgb, white_bg=white_bg)
 
     def characteristic_slices(self, z):
         """[B, 90, 90]: the prior of each latent code on the MERL characteristic slice (phi_d = 90 degrees; merl.py:78-96)."""
@@ -243,8 +234,10 @@ class Model(BaseModel):
             return brdf.reshape(z.shape[0], 90, 90)
 
     @staticmethod
-    def write_sphere_vis(outdir, id_, z, cslice, render):
-        """metadata.json, cslice.png and render.png of one identity (cslice [90, 90] reflectances, render [ims, ims, 3])."""
+    def write_sphere_vis(outdir, id_, z, cslice, render, measured=None):
+        """metadata.json, cslice.png and render.png of one identity (cslice [90, 90] reflectances, render [ims, ims, 3]); with
+        `measured` (the measured material's render, [ims, ims, 3]) also render_measured.png and 'psnr_measured' in the metadata:
+        the PSNR between the two renders clipped to [0, 1]."""
         import json
         import os
         import numpy as np
@@ -255,8 +248,14 @@ class Model(BaseModel):
         Image.fromarray(merl.characteristic_slice_as_img(to_np(cslice))).save(os.path.join(outdir, 'cslice.png'))
         u8 = (np.clip(to_np(render), 0, 1) * 255).astype(np.uint8)       # write_arr(clip=True)
         Image.fromarray(u8).save(os.path.join(outdir, 'render.png'))
+        meta = {'id': id_, 'z': [float(v) for v in to_np(z).reshape(-1)]}
+        if measured is not None:
+            a, b = np.clip(to_np(render), 0, 1).astype(np.float64), np.clip(to_np(measured), 0, 1).astype(np.float64)
+            Image.fromarray((b * 255).astype(np.uint8)).save(os.path.join(outdir, 'render_measured.png'))
+            mse = float(np.mean(np.square(a - b)))
+            meta['psnr_measured'] = 10. * np.log10(1. / mse) if mse > 0 else float('inf')
         with open(os.path.join(outdir, 'metadata.json'), 'w') as h:   # last: the files of a finished batch are all there
-            json.dump({'id': id_, 'z': [float(v) for v in to_np(z).reshape(-1)]}, h, indent=4, sort_keys=True)
+            json.dump(meta, h, indent=4, sort_keys=True)
 
     def vis_batch(self, data_dict, outdir, mode='train', dump_raw_to=None, **kwargs):
         """The raw dump; in 'test' mode also metadata.json, cslice.png (the first 90 x 90 rows of data_dict['brdf'], as the

@@ -754,6 +754,48 @@ def brdf_sphere_fwd(xyz, normal, cam, z, lxyz, lweight, blob, out=None):
     return out
 
 
+MERL_CELLS = 180 * 90 * 90
+
+
+def _merl_table(table, who):
+    table = _dev(table, 'table', (MERL_CELLS, 4))
+    if table.data_ptr() % 16:
+        raise _capi.NfxError("%s: the table must be 16-byte aligned" % who)
+    return table
+
+
+def merl_query(table, rusink, return_idx=False):
+    """rgb[n, 3] (and idx[n] int32): the valid entry of a packed MERL table (float32 [180 * 90 * 90, 4], invalid entries -1:
+    brdf.merl.MERL.device_table) nearest to each Rusinkiewicz coordinate rusink[n, 3] = (phi_d, theta_h, theta_d) in radians
+    (nfx_merl_query).  A non-finite query gives idx -1 and rgb NaN."""
+    table = _merl_table(table, 'merl_query')
+    rusink = _dev(rusink, 'rusink', (None, 3))
+    n = rusink.shape[0]
+    rgb = torch.empty((n, 3), dtype=torch.float32, device=rusink.device)
+    idx = torch.empty((n,), dtype=torch.int32, device=rusink.device) if return_idx else None
+    check(lib.nfx_merl_query(_ptr(table), _ptr(rusink), n, _ptr(rgb), _ptr(idx), _stream()), 'nfx_merl_query')
+    return (rgb, idx) if return_idx else rgb
+
+
+def merl_sphere_fwd(xyz, normal, cam, table, lxyz, lweight, return_idx=False):
+    """rgb[n, 3] (and idx[n, L] int32): a packed MERL table rendered at n sphere samples (xyz, normal [n, 3]) seen from `cam`
+    (three numbers) under the lights lxyz[L, 3] with lweight[L, 3] = light * area: the sum over the lit front-facing lights of
+    table[idx] * lweight * cos, accumulated in the kernel (nfx_merl_sphere_fwd).  idx is -1 where a row does not contribute."""
+    xyz = _dev(xyz, 'xyz', (None, 3))
+    n = xyz.shape[0]
+    normal = _dev(normal, 'normal', (n, 3))
+    table = _merl_table(table, 'merl_sphere_fwd')
+    lxyz = _dev(lxyz, 'lxyz', (None, 3))
+    nl = lxyz.shape[0]
+    lweight = _dev(lweight, 'lweight', (nl, 3))
+    cam3 = (ctypes.c_float * 3)(*[float(v) for v in (cam.tolist() if hasattr(cam, 'tolist') else cam)])
+    rgb = torch.empty((n, 3), dtype=torch.float32, device=xyz.device)
+    idx = torch.empty((n, nl), dtype=torch.int32, device=xyz.device) if return_idx else None
+    check(lib.nfx_merl_sphere_fwd(_ptr(xyz), _ptr(normal), n, ctypes.cast(cam3, ctypes.c_void_p), _ptr(table), _ptr(lxyz),
+                                  _ptr(lweight), nl, _ptr(rgb), _ptr(idx), _stream()), 'nfx_merl_sphere_fwd')
+    return (rgb, idx) if return_idx else rgb
+
+
 def _shade_common(xyz, cam, normal, albedo, rough, spec, lvis, lxyz, lareas, lvis_row=None):
     xyz = _dev(xyz, 'xyz', (None, 3))
     n = xyz.shape[0]
