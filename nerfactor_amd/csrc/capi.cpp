@@ -167,25 +167,11 @@ int nfx_nerf_pack_weights(const float* const kernels[12], const float* const bia
         return NFX_OK;
     }
     // NFX_PREC_FP32 (nerf_mlp_x3.hip): [fragments of hi = bf16(W) | fragments of lo = bf16(W - hi) | fp32 biases]
-    static const int rows[12] = {63, 256, 256, 256, 256, 319, 256, 256, 256, 256, 283, 128};
-    static const int cols[12] = {256, 256, 256, 256, 256, 256, 256, 256, 1, 256, 128, 3};
-    std::vector<std::vector<float>> lo(12);
-    const float* lo_ptr[12];
-    for (int i = 0; i < 12; ++i) {
-        const size_t n = (size_t)rows[i] * cols[i];
-        lo[i].resize(n);
-        for (size_t k = 0; k < n; ++k) {
-            const uint32_t bits = (uint32_t)pack::f32_to_bf16_rne(kernels[i][k]) << 16;
-            float hi;
-            memcpy(&hi, &bits, 4);
-            lo[i][k] = kernels[i][k] - hi;
-        }
-        lo_ptr[i] = lo[i].data();
-    }
+    const pack::LoKernels lo = pack::lo_kernels(kernels, pack::kNerfShapes, 12);
     float* b = reinterpret_cast<float*>(w + 2 * (size_t)nerf::kWeightBytes);
     std::vector<float> sink(nerf::kBiasFloats);
     if (pack_nerf_fragments(kernels, biases, w, b) ||
-        pack_nerf_fragments(lo_ptr, biases, w + nerf::kWeightBytes, sink.data()))
+        pack_nerf_fragments(lo.ptr.data(), biases, w + nerf::kWeightBytes, sink.data()))
         return nfx_fail(NFX_EINVAL, "nfx_nerf_pack_weights: internal layout mismatch");
     return NFX_OK;
 }

@@ -8,6 +8,7 @@
 
 #include "capi_common.hpp"
 #include "nerf_geom_layout.hpp"
+#include "nerf_points.hpp"
 #include "pack.hpp"
 
 extern "C" {
@@ -89,25 +90,23 @@ int nfx_nerf_pack_geom_weights(const float* const kernels[12], const float* cons
     uint8_t* w0 = static_cast<uint8_t*>(blob);
     if (prec == NFX_PREC_BF16) return pack_geom_half(kernels, biases, w0, reinterpret_cast<float*>(w0 + nerf::kGeoWeightBytes));
     // NFX_PREC_FP32 (nerf_geom_x3.hip): the chunk sequence of hi = bf16(W), then of lo = bf16(W - hi), then the floats
-    static const int rows[12] = {63, 256, 256, 256, 256, 319, 256, 256, 256, 256, 283, 128};
-    static const int cols[12] = {256, 256, 256, 256, 256, 256, 256, 256, 1, 256, 128, 3};
-    std::vector<std::vector<float>> lo(12);
-    const float* lo_ptr[12];
-    for (int i = 0; i < 12; ++i) {
-        const size_t n = (size_t)rows[i] * cols[i];
-        lo[i].resize(n);
-        for (size_t k = 0; k < n; ++k) {
-            const uint32_t bits = (uint32_t)pack::f32_to_bf16_rne(kernels[i][k]) << 16;
-            float hi;
-            memcpy(&hi, &bits, 4);
-            lo[i][k] = kernels[i][k] - hi;
-        }
-        lo_ptr[i] = lo[i].data();
-    }
+    const pack::LoKernels lo = pack::lo_kernels(kernels, pack::kNerfShapes, 12);
     std::vector<float> sink(nerf::kGeoFloats);
     int rc = pack_geom_half(kernels, biases, w0, reinterpret_cast<float*>(w0 + 2 * (size_t)nerf::kGeoWeightBytes));
     if (rc) return rc;
-    return pack_geom_half(lo_ptr, biases, w0 + nerf::kGeoWeightBytes, sink.data());
+    return pack_geom_half(lo.ptr.data(), biases, w0 + nerf::kGeoWeightBytes, sink.data());
+}
+
+// The three point descriptions of nerf_points.hpp.  A listed launch has n_pts = the list's capacity, every sample.
+static nfx::geo::Points every_sample(const float* rayo, const float* rayd, const float* z, int64_t n_rays, int n_samples) {
+    return {rayo, rayd, z, (long long)n_rays * n_samples, n_samples, nullptr, nullptr, 1, 0};
+}
+static nfx::geo::Points listed(const float* rayo, const float* rayd, const float* z, int64_t n_rays, int n_samples,
+                               const int* list, const int* count, int list_stride) {
+    return {rayo, rayd, z, (long long)n_rays * n_samples, n_samples, list, count, list_stride, 0};
+}
+static nfx::geo::Points last_samples(const float* rayo, const float* rayd, const float* z, int64_t n_rays, int n_samples) {
+    return {rayo, rayd, z, (long long)n_rays, n_samples, nullptr, nullptr, 4, 1};
 }
 
 // bf16 density of every sample: the render kernel's dataflow over the GEOM blob (nerf_sigma_v6.hip, round 6; default) or the
@@ -127,10 +126,11 @@ int nfx_nerf_sigma_fwd(const float* rayo, const float* rayd, const float* z, int
     if (n_rays == 0) return NFX_OK;
     REQUIRE(rayo && rayd && z && blob && sigma, "nfx_nerf_sigma_fwd: null pointer");
     if (!ALIGNED(blob, 16)) return nfx_fail(NFX_EALIGN, "nfx_nerf_sigma_fwd: blob must be 16-byte aligned");
-    if (prec == NFX_PREC_FP32)
-        return nfx_hip_result(nfx_launch_nerf_sigma_x3(rayo, rayd, z, (long long)n_rays * n_samples, n_samples, blob,
-                                                       sigma, nfx_option_int("nerf_blocks", 256), (hipStream_t)stream),
+    if (prec == NFX_PREC_FP32) {
+        const nfx::geo::Points pts = every_sample(rayo, rayd, z, n_rays, n_samples);
+        return nfx_hip_result(nfx_launch_nerf_sigma_x3(&pts, blob, sigma, nfx_option_int("nerf_blocks", 256), (hipStream_t)stream),
                               "nerf_sigma_fwd(fp32)");
+    }
     return nfx_hip_result(launch_sigma_bf16(rayo, rayd, z, (long long)n_rays * n_samples, n_samples, blob, sigma,
                                             (hipStream_t)stream),
                           "nerf_sigma_fwd");
@@ -156,9 +156,9 @@ int nfx_nerf_sigma_refine(const float* rayo, const float* rayd, const float* z, 
     if (n_rays == 0) return NFX_OK;
     REQUIRE(rayo && rayd && z && blob && list && count && rgbs, "nfx_nerf_sigma_refine: null pointer");
     if (!ALIGNED(blob, 16)) return nfx_fail(NFX_EALIGN, "nfx_nerf_sigma_refine: blob must be 16-byte aligned");
-    return nfx_hip_result(nfx_launch_nerf_sigma_x3_list(rayo, rayd, z, (long long)n_rays * n_samples, n_samples, blob, rgbs,
-                                                        list, count, nfx_option_int("nerf_blocks", 256),
-                                                        (hipStream_t)stream), "nerf_sigma_refine");
+    const nfx::geo::Points pts = listed(rayo, rayd, z, n_rays, n_samples, list, count, 4);
+    return nfx_hip_result(nfx_launch_nerf_sigma_x3(&pts, blob, rgbs, nfx_option_int("nerf_blocks", 256), (hipStream_t)stream),
+                          "nerf_sigma_refine");
 }
 
 int nfx_nerf_sigma_refine_last(const float* rayo, const float* rayd, const float* z, int64_t n_rays, int n_samples,
@@ -167,8 +167,8 @@ int nfx_nerf_sigma_refine_last(const float* rayo, const float* rayd, const float
     if (n_rays == 0) return NFX_OK;
     REQUIRE(rayo && rayd && z && blob && rgbs, "nfx_nerf_sigma_refine_last: null pointer");
     if (!ALIGNED(blob, 16)) return nfx_fail(NFX_EALIGN, "nfx_nerf_sigma_refine_last: blob must be 16-byte aligned");
-    return nfx_hip_result(nfx_launch_nerf_sigma_x3_last(rayo, rayd, z, (long long)n_rays, n_samples, blob, rgbs,
-                                                        nfx_option_int("nerf_blocks", 256), (hipStream_t)stream),
+    const nfx::geo::Points pts = last_samples(rayo, rayd, z, n_rays, n_samples);
+    return nfx_hip_result(nfx_launch_nerf_sigma_x3(&pts, blob, rgbs, nfx_option_int("nerf_blocks", 256), (hipStream_t)stream),
                           "nerf_sigma_refine_last");
 }
 
@@ -180,15 +180,11 @@ int nfx_nerf_sigma_grad(const float* rayo, const float* rayd, const float* z, in
     REQUIRE(rayo && rayd && z && geom_blob && normal_sigma, "nfx_nerf_sigma_grad: null pointer");
     if (!ALIGNED(geom_blob, 16) || !ALIGNED(normal_sigma, 16))
         return nfx_fail(NFX_EALIGN, "nfx_nerf_sigma_grad: blob and output must be 16-byte aligned");
-    if (prec == NFX_PREC_FP32)
-        return nfx_hip_result(nfx_launch_nerf_sigma_grad_x3(rayo, rayd, z, (long long)n_rays * n_samples, n_samples,
-                                                            geom_blob, normal_sigma,
-                                                            nfx_option_int("nerf_blocks", 256), (hipStream_t)stream),
-                              "nerf_sigma_grad(fp32)");
-    return nfx_hip_result(nfx_launch_nerf_sigma_grad(rayo, rayd, z, (long long)n_rays * n_samples, n_samples,
-                                                     geom_blob, normal_sigma, nfx_option_int("nerf_blocks", 256),
-                                                     (hipStream_t)stream),
-                          "nerf_sigma_grad");
+    const nfx::geo::Points pts = every_sample(rayo, rayd, z, n_rays, n_samples);
+    const int blocks = nfx_option_int("nerf_blocks", 256);
+    return nfx_hip_result((prec == NFX_PREC_FP32 ? nfx_launch_nerf_sigma_grad_x3 : nfx_launch_nerf_sigma_grad)(
+                              &pts, geom_blob, normal_sigma, blocks, (hipStream_t)stream),
+                          prec == NFX_PREC_FP32 ? "nerf_sigma_grad(fp32)" : "nerf_sigma_grad");
 }
 
 // the density of every sample [n_pts floats, padded to 16 bytes], then the row list (rowsel.hpp)
@@ -218,20 +214,18 @@ int nfx_nerf_sigma_grad_rows(const float* rayo, const float* rayd, const float* 
     const int* count = static_cast<const int*>(list_ws);
     const int* list = reinterpret_cast<const int*>(static_cast<char*>(list_ws) + nfx_nerf_bwd_list_bytes(n_pts)) - (n_pts + 3) / 4 * 4;
     // 1. the density of every sample (the forward-only kernel: bit-identical to the gradient kernel's own density)
-    int rc = nfx_hip_result(prec == NFX_PREC_FP32
-                                ? nfx_launch_nerf_sigma_x3(rayo, rayd, z, n_pts, n_samples, geom_blob, sigma, blocks, st)
-                                : launch_sigma_bf16(rayo, rayd, z, n_pts, n_samples, geom_blob, sigma, st),
+    const nfx::geo::Points all = every_sample(rayo, rayd, z, n_rays, n_samples);
+    int rc = nfx_hip_result(prec == NFX_PREC_FP32 ? nfx_launch_nerf_sigma_x3(&all, geom_blob, sigma, blocks, st)
+                                                  : launch_sigma_bf16(rayo, rayd, z, n_pts, n_samples, geom_blob, sigma, st),
                             "nerf_sigma_grad_rows(density)");
     if (rc) return rc;
     // 2. the samples with a density, ascending; every other sample's output row is final after this pass
     rc = nfx_hip_result(nfx_launch_select_density(sigma, n_pts, normal_sigma, list_ws, st), "nerf_sigma_grad_rows(select)");
     if (rc) return rc;
     // 3. forward + reverse sweep over the listed samples only
-    return nfx_hip_result(prec == NFX_PREC_FP32
-                              ? nfx_launch_nerf_sigma_grad_x3_list(rayo, rayd, z, n_pts, n_samples, geom_blob, normal_sigma,
-                                                                   list, count, blocks, st)
-                              : nfx_launch_nerf_sigma_grad_list(rayo, rayd, z, n_pts, n_samples, geom_blob, normal_sigma,
-                                                                list, count, blocks, st),
+    const nfx::geo::Points pts = listed(rayo, rayd, z, n_rays, n_samples, list, count, 4);
+    return nfx_hip_result((prec == NFX_PREC_FP32 ? nfx_launch_nerf_sigma_grad_x3 : nfx_launch_nerf_sigma_grad)(
+                              &pts, geom_blob, normal_sigma, blocks, st),
                           "nerf_sigma_grad_rows(gradient)");
 }
 
@@ -247,11 +241,11 @@ int nfx_nerf_sigma_fwd_list(const float* rayo, const float* rayd, const float* z
     if (!ALIGNED(blob, 16)) return nfx_fail(NFX_EALIGN, "nfx_nerf_sigma_fwd_list: blob must be 16-byte aligned");
     const int blocks = nfx_option_int("nerf_blocks", 256);
     hipStream_t st = (hipStream_t)stream;
-    return nfx_hip_result(prec == NFX_PREC_FP32
-                              ? nfx_launch_nerf_sigma_x3_list_flat(rayo, rayd, z, n_pts, n_samples, blob, sigma, list, count,
-                                                                   blocks, st)
-                              : nfx_launch_nerf_sigma_v6_list(rayo, rayd, z, n_pts, n_samples, blob, sigma, list, count,
-                                                              blocks, st),
+    if (prec == NFX_PREC_FP32) {
+        const nfx::geo::Points pts = listed(rayo, rayd, z, n_rays, n_samples, list, count, 1);
+        return nfx_hip_result(nfx_launch_nerf_sigma_x3(&pts, blob, sigma, blocks, st), "nerf_sigma_fwd_list");
+    }
+    return nfx_hip_result(nfx_launch_nerf_sigma_v6_list(rayo, rayd, z, n_pts, n_samples, blob, sigma, list, count, blocks, st),
                           "nerf_sigma_fwd_list");
 }
 

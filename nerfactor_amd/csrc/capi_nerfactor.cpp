@@ -75,26 +75,13 @@ int nfx_mlp128_pack_weights(const float* const kernels[5], const float* const bi
     const int in_dims = in_dims_of(in_kind, z_dim);
     uint8_t* w = static_cast<uint8_t*>(blob);
     if (prec == NFX_PREC_FP32) {
-        static const int out_cols[5] = {128, 128, 128, 128, 0};
-        std::vector<std::vector<float>> lo(5);
-        const float* lo_ptr[5];
-        for (int i = 0; i < 5; ++i) {
-            const int rows = i == 0 ? in_dims : i == 3 ? 128 + in_dims : 128;
-            const size_t cnt = (size_t)rows * (i == 4 ? out_dim : out_cols[i]);
-            lo[i].resize(cnt);
-            for (size_t k = 0; k < cnt; ++k) {
-                const uint32_t bits = (uint32_t)f32_to_bf16_rne(kernels[i][k]) << 16;
-                float hi;
-                memcpy(&hi, &bits, 4);
-                lo[i][k] = kernels[i][k] - hi;
-            }
-            lo_ptr[i] = lo[i].data();
-        }
+        const Shape shapes[5] = {{in_dims, 128}, {128, 128}, {128, 128}, {128 + in_dims, 128}, {128, out_dim}};
+        const LoKernels lo = lo_kernels(kernels, shapes, 5);
         const size_t wb = nfx_mlp128_x3_weight_bytes(in_kind);
         std::vector<float> sink(kMainBiasFloats);
         memset(w, 0, need);
         if (pack_m128_x3_half(kernels, biases, in_kind, z_dim, out_dim, w, reinterpret_cast<float*>(w + 2 * wb)) ||
-            pack_m128_x3_half(lo_ptr, biases, in_kind, z_dim, out_dim, w + wb, sink.data()))
+            pack_m128_x3_half(lo.ptr.data(), biases, in_kind, z_dim, out_dim, w + wb, sink.data()))
             return nfx_fail(NFX_EINVAL, "nfx_mlp128_pack_weights: layout mismatch (fp32)");
         return NFX_OK;
     }

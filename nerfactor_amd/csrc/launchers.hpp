@@ -10,6 +10,7 @@
 
 namespace nfx::generic { struct Args; struct EmbedArgs; struct BwdArgs; struct WgradArgs; }   // mlp_generic.hpp
 namespace nfx::rowsgeom { struct Args; }                                                      // brdf_rows_geom.hpp
+namespace nfx::geo { struct Points; }                                                         // nerf_points.hpp
 
 // Host-side description of one weight-gradient GEMM of a batched launch (train.hip; capi_train.cpp fills these).
 struct nfx_wgrad_call {
@@ -95,27 +96,14 @@ int nfx_launch_nerf_bwd(const float* rayo, const float* rayd, const float* z, lo
                         const float* d_rgbs, void* wsp, long long ld, int max_blocks, hipStream_t st, void* list_ws);
 // ---- nerf_fold.hip
 int nfx_launch_nerf_fold(const void* blob, void* out, hipStream_t stream);
-// ---- nerf_geom.hip
-int nfx_launch_nerf_sigma_grad_list(const float* rayo, const float* rayd, const float* z, long long n_pts, int n_samples, const void* blob,
-                                    float* out, const int* list, const int* count, int max_blocks, hipStream_t st);
-int nfx_launch_nerf_sigma_grad(const float* rayo, const float* rayd, const float* z, long long n_pts, int n_samples, const void* blob,
-                               float* out, int max_blocks, hipStream_t st);
+// ---- nerf_geom.hip (the gradient launchers take the every-sample and the list form of Points, and refuse the last-sample one)
+int nfx_launch_nerf_sigma_grad(const nfx::geo::Points* pts, const void* blob, float* out, int max_blocks, hipStream_t st);
 int nfx_launch_select_density(const float* sigma, long long n_pts, float* out, void* list_ws, hipStream_t st);
 int nfx_launch_nerf_sigma_geo(const float* rayo, const float* rayd, const float* z, long long n_pts, int n_samples, const void* blob,
                               float* out, int max_blocks, hipStream_t st);
 // ---- nerf_geom_x3.hip
-int nfx_launch_nerf_sigma_grad_x3(const float* rayo, const float* rayd, const float* z, long long n_pts, int n_samples, const void* blob,
-                                  float* out, int max_blocks, hipStream_t st);
-int nfx_launch_nerf_sigma_x3(const float* rayo, const float* rayd, const float* z, long long n_pts, int n_samples, const void* blob,
-                             float* out, int max_blocks, hipStream_t st);
-int nfx_launch_nerf_sigma_grad_x3_list(const float* rayo, const float* rayd, const float* z, long long n_pts, int n_samples,
-                                       const void* blob, float* out, const int* list, const int* count, int max_blocks, hipStream_t st);
-int nfx_launch_nerf_sigma_x3_list(const float* rayo, const float* rayd, const float* z, long long n_pts, int n_samples, const void* blob,
-                                  float* rgbs, const int* list, const int* count, int max_blocks, hipStream_t st);
-int nfx_launch_nerf_sigma_x3_list_flat(const float* rayo, const float* rayd, const float* z, long long n_pts, int n_samples,
-                                       const void* blob, float* out, const int* list, const int* count, int max_blocks, hipStream_t st);
-int nfx_launch_nerf_sigma_x3_last(const float* rayo, const float* rayd, const float* z, long long n_rays, int n_samples, const void* blob,
-                                  float* rgbs, int max_blocks, hipStream_t st);
+int nfx_launch_nerf_sigma_grad_x3(const nfx::geo::Points* pts, const void* blob, float* out, int max_blocks, hipStream_t st);
+int nfx_launch_nerf_sigma_x3(const nfx::geo::Points* pts, const void* blob, float* out, int max_blocks, hipStream_t st);
 // ---- nerf_mlp.hip
 int nfx_launch_nerf_mlp_bf16(const float* rayo, const float* rayd, const float* z, long long n_pts, int n_samples, const void* blob,
                              float* out, int variant, int max_blocks, hipStream_t stream);
@@ -135,9 +123,7 @@ int nfx_launch_nerf_sigma_v6(const float* rayo, const float* rayd, const float* 
 int nfx_launch_nerf_sigma_v6_list(const float* rayo, const float* rayd, const float* z, long long capacity, int n_samples, const void* blob,
                                   float* out, const int* list, const int* count, int max_blocks, hipStream_t stream);
 // ---- nerf_sigma_x3_pipe.hip
-int nfx_launch_nerf_sigma_x3_pipe(const float* rayo, const float* rayd, const float* z, long long n_pts, int n_samples, const void* blob,
-                                  float* out, const int* list, const int* count, int list_stride, int last_sample, int max_blocks,
-                                  hipStream_t st);
+int nfx_launch_nerf_sigma_x3_pipe(const nfx::geo::Points* pts, const void* blob, float* out, int max_blocks, hipStream_t st);
 // ---- occgrid.hip
 size_t nfx_occgrid_list_bytes(long long n_pts);
 int nfx_launch_occgrid_select(const float* rayo, const float* rayd, const float* z, long long n_rays, int n_samples, const uint32_t* bits,

@@ -1,11 +1,10 @@
 // nerf_geom.hip — density and its spatial gradient at sample points: sigma_raw(x) = sigma_out(enc(posenc(x))) and
-// n(x) = -normalize(d relu(sigma_raw) / dx), the per-sample "normal" of geometry_from_nerf.py:280-297 (there a
-// GradientTape.batch_jacobian through embedder + fine_enc + fine_sigma_out).  One fused kernel: forward through the
-// 8x256 encoder keeping 1-bit ReLU masks, reverse sweep with the transposed weights in the same register-resident
-// MFMA dataflow, input-gradient tiles landing in the positional-encoding SLOT layout, analytic posenc Jacobian.
-#include "feat_store.hpp"
+// n(x) = -normalize(d relu(sigma_raw) / dx), with bf16 operands: the policy geo::Bf16 of nerf_geom_body.hpp (which holds
+// the density march, the forward ladder and the reverse sweep), the gradient kernel's tile loop and posenc Jacobian, the
+// density kernel as a wrapper of the body, their launchers, and the selection of the samples with a density for the list form.
+#include "mlp_engine.hpp"
 #include "rowsel.hpp"
-#include "nerf_geom_layout.hpp"
+#include "nerf_geom_body.hpp"
 #include "launchers.hpp"
 
 namespace nfx {
@@ -13,129 +12,89 @@ namespace geo {
 
 constexpr int kNW = 4;
 constexpr int kRows = kNW * 32;
-constexpr int kLds = 2 * kSlotBytes + nerf::kGeoFloats * 4;
-constexpr int kNLD = 4;  // every backward chunk: 16 fragments
 
-template <int KS1, int KS2, int NL_SELF, int NL_NEXT, int KS1A, int KS2A>
-__device__ __forceinline__ void fwd_layer(WStream& ws, int tid, const float* bias, const bf16x8 (&b1)[KS1A][1],
-                                          const bf16x8 (&b2)[KS2A][1], bf16x8 (&bout)[16][1], unsigned (&m)[4]) {
-    static_for<0, 8>([&](auto T) {
-        constexpr int t = decltype(T)::value;
-        f32x16 acc[1];
-        tile_raw<KS1, KS2, (t == 7 ? NL_NEXT : NL_SELF), kNW>(ws, tid, bias + 32 * t, b1, b2, acc);
-        const unsigned bits = bwd::relu_bits16(acc[0]);
-        if constexpr (t & 1) m[t >> 1] |= bits << 16;
-        else m[t >> 1] = bits;
-        acc_to_b<true, 1>(acc, bout[2 * t], bout[2 * t + 1]);
-    });
-}
+// bf16 operands: one MFMA per product, tiles on mlp_engine.hpp's register-staged WStream
+template <int NW>
+struct Bf16 {
+    using Op = bf16x8[1];
+    using Stream = WStream;
+    static constexpr int kNW = NW;
+    static constexpr size_t kFloatOffset = nerf::kGeoWeightBytes;
+    // density only: encoder biases + the sigma bias tile
+    template <bool GRAD>
+    static constexpr int n_floats() { return GRAD ? nerf::kGeoFloats : nerf::kGeoWSig; }
+    template <bool GRAD>
+    static constexpr bool kMasks = GRAD;
+    __device__ __forceinline__ static float* floats(char* smem) { return reinterpret_cast<float*>(smem + 2 * kSlotBytes); }
+    template <bool GRAD>
+    __device__ __forceinline__ static void open(WStream& ws, char* smem, const char* blob, float*, int tid) {
+        ws.gbase = reinterpret_cast<const u32x4*>(blob);
+        ws.gend = reinterpret_cast<const u32x4*>(blob + (GRAD ? (size_t)nerf::kGeoWeightBytes : (size_t)nerf::kGeoFwdFrags * kFragBytes));
+        ws.gnext = ws.gbase;
+        ws.ring = smem;
+        stream_prologue<nerf::kNL0, NW>(ws, tid);
+    }
+    __device__ __forceinline__ static void posenc(const float (&x)[3], int h, Op (&pe)[4]) { nfx::posenc<10, 1>(x, h, 0, pe); }
+    __device__ __forceinline__ static void relu_to(const f32x16& acc, Op& lo8, Op& hi8) {
+        const f32x16 a[1] = {acc};
+        acc_to_b<true, 1>(a, lo8, hi8);
+    }
+    __device__ __forceinline__ static void put(Op (&dst)[16], int t, int r, float v) { dst[2 * t + (r >> 3)][0][r & 7] = (__bf16)v; }
+    __device__ __forceinline__ static float sigma(const f32x16& acc, int p) { return __shfl(acc[0], p, 64); }
+    template <int KS1, int KS2, int NL, int KS1A, int KS2A>
+    __device__ __forceinline__ static void tile(WStream& ws, int tid, const float* bias, const Op (&b1)[KS1A], const Op (&b2)[KS2A], f32x16& acc) {
+        f32x16 a[1];
+        tile_raw<KS1, KS2, NL, NW>(ws, tid, bias, b1, b2, a);
+        acc = a[0];
+    }
+    template <int NL>
+    __device__ __forceinline__ static void tile_zero(WStream& ws, int tid, const float*, const Op (&dz)[16], f32x16& acc) {
+        f32x16 a[1];
+        tile_init<16, 0, NL, NW>(ws, tid, [&](f32x16(&i)[1]) { bwd::zero_init<1>(i); }, dz, dz, a);
+        acc = a[0];
+    }
+    // the accumulators start from `sum`: the addition happens inside the MFMA chain
+    template <int NL>
+    __device__ __forceinline__ static void tile_add(WStream& ws, int tid, const float*, const Op (&dz)[16], f32x16& sum) {
+        f32x16 a[1];
+        tile_init<16, 0, NL, NW>(ws, tid, [&](f32x16(&i)[1]) { i[0] = sum; }, dz, dz, a);
+        sum = a[0];
+    }
+};
 
-__device__ __forceinline__ void dgrad(WStream& ws, int tid, const bf16x8 (&dz)[16][1], const unsigned (&m)[4],
-                                      bf16x8 (&dout)[16][1]) {
-    static_for<0, 8>([&](auto T) {
-        constexpr int t = decltype(T)::value;
-        f32x16 acc[1];
-        tile_init<16, 0, kNLD, kNW>(ws, tid, [&](f32x16(&a)[1]) { bwd::zero_init<1>(a); }, dz, dz, acc);
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-            dout[2 * t + (r >> 3)][0][r & 7] = (__bf16)(bwd::mask_bit(m, t, r) ? acc[0][r] : 0.f);
-    });
-}
-
-// d posenc-slot accumulators += (input rows of a layer)^T dz: 2 tiles = 32 slots per lane half
-template <int NL_LAST>
-__device__ __forceinline__ void input_grad(WStream& ws, int tid, const bf16x8 (&dz)[16][1], f32x16 (&dpe)[2]) {
-    static_for<0, 2>([&](auto T) {
-        constexpr int t = decltype(T)::value;
-        f32x16 acc[1];
-        tile_init<16, 0, (t == 1 ? NL_LAST : kNLD), kNW>(
-            ws, tid, [&](f32x16(&a)[1]) { a[0] = dpe[t]; }, dz, dz, acc);
-        dpe[t] = acc[0];
-    });
-}
-
-// LIST (round 6): the points are the flat sample indices list[0 .. *count) — the samples whose density is positive
-// (nfx_nerf_sigma_grad_rows: d relu(sigma) / dx of every other sample is zero, its output row is written by the selecting pass)
-// — and point list[c]'s result goes to out[list[c]].  A workgroup with no tile leaves before it touches the weight stream.
+// LIST: the points are the listed samples (nerf_points.hpp); a compile-time argument here, so that the every-sample kernel
+// holds no list code
 template <bool LIST>
 __global__ __launch_bounds__(kNW * 64, 1) void nerf_sigma_grad_kernel(
     const float* __restrict__ rayo, const float* __restrict__ rayd, const float* __restrict__ zbuf, long long n_pts,
     int n_samples, const char* __restrict__ blob, float4* __restrict__ out, const int* __restrict__ list,
     const int* __restrict__ count) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    using namespace nerf;
-    if constexpr (LIST) {
-        n_pts = *count;
-        if ((long long)blockIdx.x * kRows >= n_pts) return;
-    }
+    // the gradient forms of nerf_points.hpp: every sample or a list; stride and last-sample do not apply
+    if constexpr (LIST) __builtin_assume(list != nullptr);   // Points tests the pointer: the list kernel keeps no every-sample code
+    const Points pts{rayo, rayd, zbuf, n_pts, n_samples, LIST ? list : nullptr, count, 4, 0};
+    using A = Bf16<kNW>;
+    // The tile loop and the Jacobian stand in the kernel itself, not behind a function: only so does the compiler give the
+    // parent's instruction selection (nerf_geom_body.hpp, profiles/geom_body/).  The lines from counted() to sample() are
+    // nerf_sigma_body()'s, the Jacobian is normal_sigma()'s: they change together.
+    long long n;
+    if (!pts.counted(kRows, n)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, p = lane & 31;
-    float* fl = reinterpret_cast<float*>(smem + 2 * kSlotBytes);
-    {
-        const float* src = reinterpret_cast<const float*>(blob + kGeoWeightBytes);
-        for (int i = tid; i < kGeoFloats; i += kNW * 64) fl[i] = src[i];
-    }
-    WStream ws;
-    ws.gbase = reinterpret_cast<const u32x4*>(blob);
-    ws.gend = reinterpret_cast<const u32x4*>(blob + kGeoWeightBytes);
-    ws.gnext = ws.gbase;
-    ws.ring = smem;
-    stream_prologue<kNL0, kNW>(ws, tid);
-    const long long n_tiles = (n_pts + kRows - 1) / kRows;
+    WStream st;
+    const float* fl = start<A, true>(st, smem, blob, tid);
+    const long long n_tiles = (n + kRows - 1) / kRows;
     for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const long long row = tile * kRows + wave * 32 + p;
-        const bool valid = row < n_pts;
-        long long mm = valid ? row : n_pts - 1;
-        if constexpr (LIST) mm = list[mm];
+        const bool valid = row < n;
+        const long long mm = pts.sample(row, n);
         float x[3];
-        {
-            const long long ray = mm / n_samples;
-            const float zz = zbuf[mm];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) x[k] = rayo[ray * 3 + k] + rayd[ray * 3 + k] * zz;
-        }
-        bf16x8 pe[4][1];
-        posenc<10, 1>(x, h, 0, pe);
-        // ------------------------------------------------------------------ forward, masks only
+        pts.position(mm, x);
+        A::Op pe[4], ha[16], hb[16];
+        A::posenc(x, h, pe);
         unsigned mk[8][4];
-        bf16x8 ha[16][1], hb[16][1];
-        fwd_layer<4, 0, kNL0, kNLH>(ws, tid, fl + 256 * 0, pe, pe, ha, mk[0]);
-        fwd_layer<16, 0, kNLH, kNLH>(ws, tid, fl + 256 * 1, ha, pe, hb, mk[1]);
-        fwd_layer<16, 0, kNLH, kNLH>(ws, tid, fl + 256 * 2, hb, pe, ha, mk[2]);
-        fwd_layer<16, 0, kNLH, kNLH>(ws, tid, fl + 256 * 3, ha, pe, hb, mk[3]);
-        fwd_layer<16, 0, kNLH, kNL5>(ws, tid, fl + 256 * 4, hb, pe, ha, mk[4]);
-        fwd_layer<16, 4, kNL5, kNLH>(ws, tid, fl + 256 * 5, ha, pe, hb, mk[5]);
-        fwd_layer<16, 0, kNLH, kNLH>(ws, tid, fl + 256 * 6, hb, pe, ha, mk[6]);
-        fwd_layer<16, 0, kNLH, kNLH>(ws, tid, fl + 256 * 7, ha, pe, hb, mk[7]);
-        float sigma;
-        {
-            f32x16 acc[1];
-            tile_raw<16, 0, kNLD, kNW>(ws, tid, fl + kGeoBiasSig, hb, pe, acc);
-            sigma = __shfl(acc[0][0], p, 64);  // row 0 of the tile lives on the h = 0 lanes
-        }
-        // ------------------------------------------------------------------ reverse sweep
-        // dZ7 = mask7 . W_sigma (the same vector for every point: no MFMA)
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float wv = fl[kGeoWSig + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h];
-                ha[2 * t + (r >> 3)][0][r & 7] = (__bf16)(bwd::mask_bit(mk[7], t, r) ? wv : 0.f);
-            }
-        }
+        const float sigma = forward<A, true>(st, tid, fl, p, pe, ha, hb, mk);
         f32x16 dpe[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) dpe[t][r] = 0.f;
-        dgrad(ws, tid, ha, mk[6], hb);          // enc[7]^T -> dZ6
-        dgrad(ws, tid, hb, mk[5], ha);          // enc[6]^T -> dZ5
-        input_grad<kNLD>(ws, tid, ha, dpe);     // enc[5][256:]^T dZ5 -> posenc slots
-        dgrad(ws, tid, ha, mk[4], hb);          // enc[5][:256]^T -> dZ4
-        dgrad(ws, tid, hb, mk[3], ha);          // enc[4]^T -> dZ3
-        dgrad(ws, tid, ha, mk[2], hb);          // enc[3]^T -> dZ2
-        dgrad(ws, tid, hb, mk[1], ha);          // enc[2]^T -> dZ1
-        dgrad(ws, tid, ha, mk[0], hb);          // enc[1]^T -> dZ0
-        input_grad<kNL0>(ws, tid, hb, dpe);     // enc[0]^T dZ0 -> posenc slots; next chunk = L0 of the next tile
+        reverse_sweep<A>(st, tid, fl, h, mk, ha, hb, dpe);
         // ------------------------------------------------------------------ posenc Jacobian (slot q = 8 s + j)
         float g[3] = {0.f, 0.f, 0.f};
 #pragma unroll
@@ -158,84 +117,42 @@ __global__ __launch_bounds__(kNW * 64, 1) void nerf_sigma_grad_kernel(
             const float on = sigma > 0.f ? 1.f : 0.f;           // gradient of relu(sigma_raw)
             const float gx = g[0] * on, gy = g[1] * on, gz = g[2] * on;
             const float inv = -1.0f / sqrtf(fmaxf(gx * gx + gy * gy + gz * gz, 1e-12f));  // -l2_normalize(., eps 1e-12)
-            out[LIST ? mm : row] = make_float4(gx * inv, gy * inv, gz * inv, sigma);
+            out[pts.grad_row(row, mm)] = make_float4(gx * inv, gy * inv, gz * inv, sigma);
         }
     }
 }
 
-// Density only, for the shadow-ray and coarse camera marches (eval_sigma_mlp, geometry_from_nerf.py:322-350, before its
-// relu): the encoder + sigma tile are the first 65 chunks of the GEOM blob, so the weight stream wraps right after the
-// sigma tile — none of the 13 bottleneck / rgb chunks of the inference blob is fetched, staged or synchronised on.
+// Density only, for the shadow-ray and coarse camera marches; the sigma_variant = 0 identity reference of nerf_sigma_v6.hip.
 // 8 waves x 32 points like nerf_mlp_bf16_kernel<1, 8>; same arithmetic: bit-identical sigma.
 __global__ __launch_bounds__(512, 2) void nerf_sigma_geo_kernel(
     const float* __restrict__ rayo, const float* __restrict__ rayd, const float* __restrict__ zbuf, long long n_pts,
     int n_samples, const char* __restrict__ blob, float* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    using namespace nerf;
     constexpr int NW = 8;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, p = lane & 31;
     constexpr int kTilePts = NW * 32;
-    float* fl = reinterpret_cast<float*>(smem + 2 * kSlotBytes);
-    {
-        const float* src = reinterpret_cast<const float*>(blob + kGeoWeightBytes);
-        for (int i = tid; i < kGeoWSig; i += NW * 64) fl[i] = src[i];   // encoder biases + the sigma bias tile
-    }
-    WStream ws;
-    ws.gbase = reinterpret_cast<const u32x4*>(blob);
-    ws.gend = reinterpret_cast<const u32x4*>(blob + (size_t)kGeoFwdFrags * kFragBytes);
-    ws.gnext = ws.gbase;
-    ws.ring = smem;
-    stream_prologue<kNL0, NW>(ws, tid);
-    const long long n_tiles = (n_pts + kTilePts - 1) / kTilePts;
-    for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        bf16x8 pe[4][1];
-        const long long m = tile * kTilePts + wave * 32 + p;
-        {
-            const long long mm = m < n_pts ? m : n_pts - 1;
-            const long long ray = mm / n_samples;
-            const float zz = zbuf[mm];
-            float x[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) x[k] = rayo[ray * 3 + k] + rayd[ray * 3 + k] * zz;
-            posenc<10, 1>(x, h, 0, pe);
-        }
-        bf16x8 ha[16][1], hb[16][1];
-        layer<4, 0, 8, kNL0, kNLH, true, NW>(ws, tid, fl + 256 * 0, pe, pe, ha);
-        layer<16, 0, 8, kNLH, kNLH, true, NW>(ws, tid, fl + 256 * 1, ha, pe, hb);
-        layer<16, 0, 8, kNLH, kNLH, true, NW>(ws, tid, fl + 256 * 2, hb, pe, ha);
-        layer<16, 0, 8, kNLH, kNLH, true, NW>(ws, tid, fl + 256 * 3, ha, pe, hb);
-        layer<16, 0, 8, kNLH, kNL5, true, NW>(ws, tid, fl + 256 * 4, hb, pe, ha);
-        layer<16, 4, 8, kNL5, kNLH, true, NW>(ws, tid, fl + 256 * 5, ha, pe, hb);
-        layer<16, 0, 8, kNLH, kNLH, true, NW>(ws, tid, fl + 256 * 6, hb, pe, ha);
-        layer<16, 0, 8, kNLH, kNLH, true, NW>(ws, tid, fl + 256 * 7, ha, pe, hb);
-        f32x16 acc[1];
-        tile_raw<16, 0, kNL0, NW>(ws, tid, fl + kGeoBiasSig, hb, pe, acc);   // next chunk: enc[0] tile 0 again
-        if (h == 0 && m < n_pts) out[m] = acc[0][0];
-    }
+    static_assert(kTilePts == 256, "the launcher's tile");
+    const Points pts{rayo, rayd, zbuf, n_pts, n_samples, nullptr, nullptr, 1, 0};
+    nerf_sigma_body<Bf16<NW>>(pts, blob, out, smem);
 }
 
 }  // namespace geo
 }  // namespace nfx
 
-// list / count null: every point; else n_pts = the list's capacity (sizes the grid), the kernel reads the count on the device
-extern "C" int nfx_launch_nerf_sigma_grad_list(const float* rayo, const float* rayd, const float* z, long long n_pts,
-                                               int n_samples, const void* blob, float* out, const int* list,
-                                               const int* count, int max_blocks, hipStream_t st) {
+// (normal, sigma) rows of every sample (pts.list null) or of the listed ones
+extern "C" int nfx_launch_nerf_sigma_grad(const nfx::geo::Points* pts, const void* blob, float* out, int max_blocks,
+                                          hipStream_t st) {
     using namespace nfx;
-    if (n_pts <= 0) return 0;
-    const long long tiles = (n_pts + geo::kRows - 1) / geo::kRows;
+    if (pts->last_sample) return (int)hipErrorInvalidValue;   // the gradient has the every-sample and the list form only
+    if (pts->n_pts <= 0) return 0;
+    const long long tiles = (pts->n_pts + geo::kRows - 1) / geo::kRows;
     const int grid = (int)(tiles < max_blocks ? tiles : max_blocks);
-    auto k = list ? geo::nerf_sigma_grad_kernel<true> : geo::nerf_sigma_grad_kernel<false>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       geo::kLds);
+    auto k = pts->list ? geo::nerf_sigma_grad_kernel<true> : geo::nerf_sigma_grad_kernel<false>;
+    constexpr int lds = 2 * kSlotBytes + nerf::kGeoFloats * 4;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(geo::kNW * 64), geo::kLds, st, rayo, rayd, z, n_pts, n_samples,
-                       (const char*)blob, (float4*)out, list, count);
+    hipLaunchKernelGGL(k, dim3(grid), dim3(geo::kNW * 64), lds, st, pts->rayo, pts->rayd, pts->z, pts->n_pts, pts->n_samples,
+                       (const char*)blob, (float4*)out, pts->list, pts->count);
     return (int)hipGetLastError();
-}
-extern "C" int nfx_launch_nerf_sigma_grad(const float* rayo, const float* rayd, const float* z, long long n_pts,
-                                          int n_samples, const void* blob, float* out, int max_blocks, hipStream_t st) {
-    return nfx_launch_nerf_sigma_grad_list(rayo, rayd, z, n_pts, n_samples, blob, out, nullptr, nullptr, max_blocks, st);
 }
 
 // The samples with a positive density, ascending (rowsel.hpp), for the LIST form of the gradient kernels; the same pass

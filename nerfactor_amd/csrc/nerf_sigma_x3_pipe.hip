@@ -20,6 +20,7 @@
 #include "mlp_x3.hpp"
 #include "lds_dma.hpp"
 #include "nerf_geom_layout.hpp"
+#include "nerf_points.hpp"
 #include "launchers.hpp"
 
 namespace nfx {
@@ -164,18 +165,15 @@ __device__ __forceinline__ void layer(const Ctx& cx, const float* fl, const Pair
     });
 }
 
-// Point i of the launch: flat sample i (plain), list[i] (list != nullptr) or the last sample of ray i (last_sample);
-// its density goes to out[i] (plain) or to out[list_stride (sample + 1) - 1].
+// The points of the launch and where their densities go: nerf_points.hpp, as in nerf_sigma_x3_kernel<false>.
 __global__ __launch_bounds__(kNW * 64, 1) void nerf_sigma_x3_pipe_kernel(
     const float* __restrict__ rayo, const float* __restrict__ rayd, const float* __restrict__ zbuf, long long n_pts,
     int n_samples, const char* __restrict__ blob, float* __restrict__ out, const int* __restrict__ list,
     const int* __restrict__ count, int list_stride, int last_sample) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using namespace nerf;
-    if (list != nullptr) {
-        n_pts = *count;
-        if ((long long)blockIdx.x * kRows >= n_pts) return;      // no tile for this workgroup: before the weight stream
-    }
+    const geo::Points pts{rayo, rayd, zbuf, n_pts, n_samples, list, count, list_stride, last_sample};
+    if (!pts.counted(kRows, n_pts)) return;      // no tile for this workgroup: before the weight stream
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, p = lane & 31;
     float* fl = reinterpret_cast<float*>(smem + kRing * x3::kSlot);
     {
@@ -186,23 +184,15 @@ __global__ __launch_bounds__(kNW * 64, 1) void nerf_sigma_x3_pipe_kernel(
     const Ctx cx{smem, blob, (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(lds_char*)smem),
                  __builtin_amdgcn_readfirstlane(wave), lane};
     dma_chunk<0>(cx);
-    const bool indirect = list != nullptr || last_sample != 0;
     const long long n_tiles = (n_pts + kRows - 1) / kRows;
     for (long long tl = blockIdx.x; tl < n_tiles; tl += gridDim.x) {
         // ------------------------------------------------------------------ the idle position of the sequence
         dma_chunk<1>(cx);     // over the sigma tile's slot: behind the barrier that ended it
         const long long row = tl * kRows + wave * 32 + p;
         const bool valid = row < n_pts;
-        long long mm = valid ? row : n_pts - 1;
-        if (list != nullptr) mm = list[mm];
-        else if (last_sample) mm = (mm + 1) * n_samples - 1;
+        const long long mm = pts.sample(row, n_pts);
         float x[3];
-        {
-            const long long ray = mm / n_samples;
-            const float zz = zbuf[mm];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) x[k] = rayo[ray * 3 + k] + rayd[ray * 3 + k] * zz;
-        }
+        pts.position(mm, x);
         Pair pe[4];
         x3::posenc_pair<10>(x, h, pe);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // chunks 0 and 1 (and the floats) are in
@@ -224,29 +214,24 @@ __global__ __launch_bounds__(kNW * 64, 1) void nerf_sigma_x3_pipe_kernel(
         // the sigma tile (-> accs[0]); pending: the last tile of enc[7] (accs[1] -> hb[14], hb[15], complete after k-step 7)
         tile<64, 16, 0>(cx, fl, hb, pe, accs[0], accs[1], ab, pend(hb[14], hb[15]));
         const float sigma = accs[0][0];   // row 0 of the tile, on the h = 0 lanes
-        if (valid && h == 0) {
-            if (indirect) out[list_stride * (mm + 1) - 1] = sigma;
-            else out[row] = sigma;
-        }
+        if (valid && h == 0) pts.store_sigma(out, row, mm, sigma);
     }
 }
 
 }  // namespace geo3p
 }  // namespace nfx
 
-// n_pts: the points of the launch (list mode: the list's capacity, which sizes the grid; the kernel reads the real count
-// on the device; last-sample mode: the rays)
-extern "C" int nfx_launch_nerf_sigma_x3_pipe(const float* rayo, const float* rayd, const float* z, long long n_pts,
-                                             int n_samples, const void* blob, float* out, const int* list, const int* count,
-                                             int list_stride, int last_sample, int max_blocks, hipStream_t st) {
+// pts.n_pts sizes the grid (nerf_points.hpp)
+extern "C" int nfx_launch_nerf_sigma_x3_pipe(const nfx::geo::Points* pts, const void* blob, float* out, int max_blocks,
+                                             hipStream_t st) {
     using namespace nfx::geo3p;
-    if (n_pts <= 0) return 0;
-    const long long tiles = (n_pts + kRows - 1) / kRows;
+    if (pts->n_pts <= 0) return 0;
+    const long long tiles = (pts->n_pts + kRows - 1) / kRows;
     const int grid = (int)(tiles < max_blocks ? tiles : max_blocks);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(nerf_sigma_x3_pipe_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(nerf_sigma_x3_pipe_kernel, dim3(grid), dim3(kNW * 64), kLds, st, rayo, rayd, z, n_pts, n_samples,
-                       (const char*)blob, out, list, count, list_stride, last_sample);
+    hipLaunchKernelGGL(nerf_sigma_x3_pipe_kernel, dim3(grid), dim3(kNW * 64), kLds, st, pts->rayo, pts->rayd, pts->z, pts->n_pts,
+                       pts->n_samples, (const char*)blob, out, pts->list, pts->count, pts->list_stride, pts->last_sample);
     return (int)hipGetLastError();
 }

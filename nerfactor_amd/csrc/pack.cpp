@@ -14,6 +14,27 @@ uint16_t f32_to_bf16_rne(float f) {
     return (uint16_t)(u >> 16);
 }
 
+const Shape kNerfShapes[12] = {{63, 256},  {256, 256}, {256, 256}, {256, 256}, {256, 256}, {319, 256},
+                               {256, 256}, {256, 256}, {256, 1},   {256, 256}, {283, 128}, {128, 3}};
+
+LoKernels lo_kernels(const float* const* kernels, const Shape* shapes, int n) {
+    LoKernels lo;
+    lo.data.resize(n);
+    lo.ptr.resize(n);
+    for (int i = 0; i < n; ++i) {
+        const size_t cnt = (size_t)shapes[i].rows * shapes[i].cols;
+        lo.data[i].resize(cnt);
+        for (size_t k = 0; k < cnt; ++k) {
+            const uint32_t bits = (uint32_t)f32_to_bf16_rne(kernels[i][k]) << 16;
+            float hi;
+            memcpy(&hi, &bits, 4);
+            lo.data[i][k] = kernels[i][k] - hi;
+        }
+        lo.ptr[i] = lo.data[i].data();
+    }
+    return lo;
+}
+
 int seg_ksteps(const Seg& s) {
     switch (s.kind) {
         case kHidden: return s.n / 16;

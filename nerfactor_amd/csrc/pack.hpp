@@ -40,5 +40,18 @@ size_t pack_layer_bf16(const std::vector<Seg>& segs, const std::vector<Src>& src
 
 uint16_t f32_to_bf16_rne(float f);
 
+// The fp32-class blobs (NFX_PREC_FP32) hold every kernel twice: the fragments of hi = bf16(W), then of lo = bf16(W - hi).
+// lo_kernels() gives the fp32 kernels W - hi, to be packed like the kernels themselves.
+struct Shape {
+    int rows, cols;   // a Keras Dense kernel [in, out]
+};
+// enc[0..7] (enc[5] takes the skip input), sigma_out, bottleneck, rgb[0] (+ the view encoding), rgb[1]
+extern const Shape kNerfShapes[12];
+struct LoKernels {
+    std::vector<std::vector<float>> data;
+    std::vector<const float*> ptr;   // ptr[i] = data[i].data(): what the packers take
+};
+LoKernels lo_kernels(const float* const* kernels, const Shape* shapes, int n);
+
 }  // namespace pack
 }  // namespace nfx

@@ -2,7 +2,10 @@
 """Secondary benchmark: geometry_from_nerf on one synthetic view — camera march with density
 gradients (128 + 320 samples per ray) and shadow-ray march to 512 lights; 128 coarse + 192 importance samples per ray (the fine pass evaluates all 320).
 
-    python scripts/bench_geometry.py [--imh 256] [--surf 4096]
+    python scripts/bench_geometry.py [--imh 256] [--surf 4096] [--prec bf16|fp32]
+
+--prec fp32: the model's `precision`, so that both marches run the fp32-class gradient and density kernels (nerf_geom_x3.hip,
+nerf_sigma_x3_pipe.hip).
 """
 import argparse
 import json
@@ -21,6 +24,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--imh', type=int, default=256)
     ap.add_argument('--surf', type=int, default=4096, help="surface points marched towards the 512 lights")
+    ap.add_argument('--prec', choices=('bf16', 'fp32'), default='bf16', help="MFMA operand type of the model")
     args = ap.parse_args()
     from nerfactor_amd import build
     build.build()
@@ -30,7 +34,7 @@ def main():
     from tests import common
     dev = torch.device('cuda', 0)
     torch.manual_seed(0)
-    cfg = make_config('nerf')
+    cfg = make_config('nerf', precision=args.prec)
     model = get_model_class('nerf')(cfg).to(dev)
     with torch.no_grad():
         for pref in ('coarse_', 'fine_'):
@@ -61,6 +65,7 @@ def main():
     enc_flop = 2 * (63 * 256 + 6 * 256 * 256 + 319 * 256 + 256)          # encoder + sigma_out, per density sample
     out = {
         "workload": "geometry_from_nerf, %dx%d view, 128 coarse + 320 fine-net samples per ray" % (args.imh, args.imh),
+        "prec": args.prec,
         "depth_normal_ms": (t1 - t0) * 1e3, "rays_per_s": n / (t1 - t0),
         # coarse forward 128 samples; fine forward + reverse sweep (~1x the forward MACs) on 320 samples
         "depth_normal_tflops": n * (128 + 2 * 320) * enc_flop / (t1 - t0) / 1e12,

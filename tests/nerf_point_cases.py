@@ -1,5 +1,5 @@
 """Inputs and oracles for the NeRF point kernels (nerf_mlp_v6.hip and nerf_sigma_v6.hip on nerf_v6_engine.hpp, nerf_mlp.hip,
-nerf_mlp_x3.hip, nerf_geom.hip, nerf_geom_x3.hip, nerf_sigma_x3_pipe.hip): no GPU here.
+nerf_mlp_x3.hip, nerf_geom.hip and nerf_geom_x3.hip on nerf_geom_body.hpp, nerf_sigma_x3_pipe.hip): no GPU here.
 
 Every one of these kernels gives a lane the flat point index m, reads z[m] and finds the ray with ray = m / n_samples.  What
 the older shapes cannot do, these inputs do:
@@ -44,11 +44,27 @@ SOURCE_CONSTANTS = [
     ('mlp_x3.hpp', r'constexpr int kNW = 4;'),
     ('nerf_mlp_x3.hip', r'constexpr int kTilePts = kNW \* 32;'),
     ('nerf_mlp_x3.hip', r'const long long mm = m < n_pts \? m : n_pts - 1;\s*const long long ray = mm / n_samples;'),
+    # nerf_geom_body.hpp: the density march (the gradient kernels hold the same lines in their __global__ functions); a policy's kNW waves x 32 points per tile
+    ('nerf_geom_body.hpp', r'constexpr int kRows = A::kNW \* 32;'),
+    ('nerf_geom_body.hpp', r'const long long row = tile \* kRows \+ wave \* 32 \+ p;\s*const bool valid = row < n_pts;\s*const long long mm = pts.sample\(row, n_pts\);'),
     ('nerf_geom.hip', r'constexpr int kNW = 4;\s*constexpr int kRows = kNW \* 32;'),
+    ('nerf_geom.hip', r'static constexpr int kNW = NW;'),
+    ('nerf_geom.hip', r'using A = Bf16<kNW>;'),
+    ('nerf_geom.hip', r'const long long row = tile \* kRows \+ wave \* 32 \+ p;\s*const bool valid = row < n;\s*const long long mm = pts.sample\(row, n\);'),
     ('nerf_geom.hip', r'constexpr int NW = 8;'),
     ('nerf_geom.hip', r'constexpr int kTilePts = NW \* 32;'),
+    ('nerf_geom.hip', r'nerf_sigma_body<Bf16<NW>>\(pts, blob, out, smem\);'),
     ('nerf_geom_x3.hip', r'constexpr int kNW = x3::kNW;\s*constexpr int kRows = kNW \* 32;'),
+    ('nerf_geom_x3.hip', r'static constexpr int kNW = x3::kNW;'),
+    ('nerf_geom_x3.hip', r'const long long row = tile \* kRows \+ wave \* 32 \+ p;\s*const bool valid = row < n;\s*const long long mm = pts.sample\(row, n\);'),
     ('nerf_sigma_x3_pipe.hip', r'constexpr int kNW = x3::kNW;\s*constexpr int kRows = kNW \* 32;'),
+    ('nerf_sigma_x3_pipe.hip', r'const long long row = tl \* kRows \+ wave \* 32 \+ p;\s*const bool valid = row < n_pts;\s*const long long mm = pts.sample\(row, n_pts\);'),
+    # nerf_points.hpp: position m -> flat sample (every sample, listed, last sample of ray m) -> ray, and where the density goes
+    ('nerf_points.hpp', r'long long mm = m < n_pts \? m : n_pts - 1;\s*if \(list != nullptr\) mm = list\[mm\];\s*else if \(last_sample\) mm = \(mm \+ 1\) \* n_samples - 1;'),
+    ('nerf_points.hpp', r'const long long ray = mm / n_samples;\s*const float zz = z\[mm\];'),
+    ('nerf_points.hpp', r'if \(list != nullptr \|\| last_sample\) out\[list_stride \* \(mm \+ 1\) - 1\] = sigma;\s*else out\[m\] = sigma;'),
+    ('nerf_points.hpp', r'return list != nullptr \? mm : m;'),
+    ('nerf_points.hpp', r'n = \*count;\s*if \(\(long long\)blockIdx.x \* tile_rows >= n\) return false;'),
     ('capi.cpp', r'nfx_option_int\("nerf_blocks", 256\)'),
     ('capi.cpp', r'nfx_option_int\("nerf_variant", 7\)'),
 ]

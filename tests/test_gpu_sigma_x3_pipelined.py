@@ -3,10 +3,14 @@
 order, so the same bits — in plain mode, in both list modes and through the one-launch refinement of every ray's last sample
 (nfx_nerf_sigma_refine_last).  Shapes: the smallest at which the kernel takes another path (one point, a partial and an exact
 128-point tile, one point more, a tile that spans rays, and 256 x 128 + 1 points: the first count at which a workgroup of the
-256-block grid runs a second tile, so the weight ring wraps from the sigma chunk back to chunk 0)."""
+256-block grid runs a second tile, so the weight ring wraps from the sigma chunk back to chunk 0).  Both kernels take "which
+sample is point m, where does its density go" from csrc/nerf_points.hpp: the 840 points of tests/nerf_point_cases.py go
+through both in the two list forms and the last-sample form."""
 import numpy as np
 import pytest
 import torch
+
+from tests import common, nerf_point_cases as pc
 
 pytestmark = pytest.mark.gpu
 
@@ -121,3 +125,48 @@ def test_last_sample_entry_leaves_a_one_sample_ray_alone(nfx_lib, cuda, blobs):
     rgbs = before.clone()
     assert ops.nerf_refine_last_sample(o, d, z, rgbs, blobs[0]) is rgbs
     assert torch.equal(rgbs, before)
+
+
+@pytest.mark.parametrize('s', [105, 7])
+@pytest.mark.parametrize('name', pc.SETS)
+def test_the_840_points_have_the_old_kernel_s_bits_in_every_point_form(nfx_lib, cuda, nfx_opt, name, s):
+    """List with stride 4 (nfx_nerf_sigma_refine, the kernel call of nerf_refine_coarse), list with stride 1
+    (nerf_sigma_fwd_list) and last sample (nerf_refine_last_sample) on the 840-point sets, as [8, 105] and [120, 7]: both
+    kernels write the same bits, they are nerf_sigma_fwd's at those samples, and nothing else is written.  The list is 333
+    samples in no order: two 128-point tiles and a partial one."""
+    from nerfactor_amd import ops
+    ps = pc.point_set(name)
+    blob = ops.pack_nerf_geom_weights(*common.nerf_layers(ps.net), prec='fp32').to(cuda)
+    o, d, z = (torch.from_numpy(np.array(a)).to(cuda) for a in ps.layout(s))
+    n = pc.N // s
+    want = ops.nerf_sigma_fwd(o, d, z, blob, 'fp32').reshape(-1)
+    picked = np.random.default_rng(840).permutation(pc.N)[:333]
+    lst = torch.full((pc.N,), -1, dtype=torch.int32, device=cuda)
+    lst[:333] = torch.from_numpy(picked.astype(np.int32)).to(cuda)
+    cnt = torch.tensor([333], dtype=torch.int32, device=cuda)
+    listed = torch.zeros(pc.N, dtype=torch.bool, device=cuda)
+    listed[torch.from_numpy(picked).to(cuda)] = True
+    last = torch.zeros(n, s, dtype=torch.bool, device=cuda)
+    last[:, -1] = True
+    p = ops._ptr
+
+    def stride4():
+        out = torch.full((n, s, 4), SENTINEL, device=cuda)
+        nfx_lib.check(nfx_lib.lib.nfx_nerf_sigma_refine(p(o), p(d), p(z), n, s, p(blob), p(lst), p(cnt), p(out), ops._stream()),
+                      'nfx_nerf_sigma_refine')
+        return out
+
+    def stride1():
+        return ops.nerf_sigma_fwd_list(o, d, z, blob, lst, cnt, torch.full((n, s), SENTINEL, device=cuda), 'fp32')
+
+    def last_sample():
+        return ops.nerf_refine_last_sample(o, d, z, torch.full((n, s, 4), SENTINEL, device=cuda), blob)
+
+    for form, written in ((stride4, listed), (stride1, listed), (last_sample, last.reshape(-1))):
+        old, new = _both(nfx_opt, form)
+        assert torch.equal(new.view(torch.int32), old.view(torch.int32)), (form.__name__, int((new != old).sum()))
+        sig = new.reshape(-1) if form is stride1 else new[..., 3].reshape(-1)
+        assert torch.equal(sig[written], want[written]), form.__name__
+        assert bool((sig[~written] == SENTINEL).all()), form.__name__
+        if form is not stride1:
+            assert bool((new[..., :3] == SENTINEL).all()), form.__name__
