@@ -8,7 +8,7 @@
 //   d z_i      = dx[z slots]                                                  (summed over the lights)
 //   d rusink_k = dx[r_k] + sum_b 2^b ( cos(2^b r_k) dx[sin] - sin(2^b r_k) dx[cos] )
 //   d normal   = J^T d rusink,  J = d rusink / d normal by forward-mode duals (geom_ad.hpp)
-#include "geom.hpp"
+#include "brdf_row.hpp"
 #include "geom_ad.hpp"
 #include "mlp128_layout.hpp"
 #include "mlp_engine.hpp"
@@ -135,23 +135,12 @@ __global__ __launch_bounds__(kNW * 64, 1) void brdf_spec_bwd_kernel(
         float lz;
         rusink_dual(nr, ldir, vdir, rus, lz);
         const bool front = lz > 0.0f;
-        // ---- forward input (same slots as brdf_spec_kernel)
+        // ---- forward input (brdf_row.hpp: the slots of brdf_spec_kernel) from the values of the duals
+        const float rv[3] = {rus[0].v, rus[1].v, rus[2].v};
         float v[16];
-#pragma unroll
-        for (int q = 0; q < 6; ++q) v[q] = sin_shifted_small(rus[q % 3].v * (float)(1 << (q / 3)), h);
-        v[6] = h ? rus[2].v : rus[0].v;
-        v[7] = h ? z[pt * z_dim] : rus[1].v;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int i = 1 + 2 * j + h;
-            v[8 + j] = i < z_dim ? z[pt * z_dim + i] : 0.0f;
-        }
+        brdf_fill_slots(rv, z + pt * z_dim, z_dim, h, v);
         bf16x8 bin[2][1];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) bin[s][0][j] = (__bf16)v[8 * s + j];
-        }
+        brdf_cast_slots(v, bin, 0);
         // ---- forward (re-computed)
         bf16x8 h0[8][1], h1[8][1], h2[8][1], h3[8][1];
         layer<2, 0, 4, 1, 2, true, kNW>(ws, tid, bias_lds, bin, bin, h0);
@@ -340,21 +329,9 @@ __global__ __launch_bounds__(kNW * 64, 1) void brdf_rows_kernel(
         if (rc >= n) rus[0] = rus[0] + 3.14159265358979323846f;   // brdf.py:103
         const float* zp = z + src * z_dim;
         float v[16];
-#pragma unroll
-        for (int q = 0; q < 6; ++q) v[q] = sin_shifted_small(rus[q % 3] * (float)(1 << (q / 3)), h);
-        v[6] = h ? rus[2] : rus[0];
-        v[7] = h ? zp[0] : rus[1];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int i = 1 + 2 * j + h;
-            v[8 + j] = i < z_dim ? zp[i] : 0.0f;
-        }
+        brdf_fill_slots(rus, zp, z_dim, h, v);
         bf16x8 bin[2][1];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) bin[s][0][j] = (__bf16)v[8 * s + j];
-        }
+        brdf_cast_slots(v, bin, 0);
         bf16x8 h0[8][1], h1[8][1], h2[8][1], h3[8][1];
         layer<2, 0, 4, 1, 2, true, kNW>(ws, tid, bias_lds, bin, bin, h0);
         layer<8, 0, 4, 2, 2, true, kNW>(ws, tid, bias_lds + 128, h0, bin, h1);

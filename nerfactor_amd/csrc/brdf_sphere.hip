@@ -4,10 +4,10 @@
 //
 // Rows.  A (sample, light) row is the row of the default nfx_brdf_spec_fwd (brdf_compact_kernel<4, 1, 4>, lvis_v2.hip):
 // front-lit decision and cosine from dir_to / world2local / mat3_apply (geom.hpp), closed-form Rusinkiewicz inputs
-// (brdf_point_frame + brdf_row_angles below: the same statements as lvis_v2.hip's, which stays untouched because the
-// bit-for-bit suites pin its code object; -ffp-contract=off makes equal statements equal bits), the packed fragments of
-// mlp128_layout.hpp resident in LDS, bias-initialised accumulators, k-steps in ascending order, bf16 ReLU epilogue
-// (mlp_engine.hpp), softplus.  The specular value of a row is the same bits as that kernel's.
+// (brdf_point_frame + brdf_row_angles of brdf_row.hpp, the functions that kernel calls), the packed fragments of
+// mlp128_layout.hpp resident in LDS (mlp128_resident.hpp: size and fragment offsets), bias-initialised accumulators,
+// k-steps in ascending order, bf16 ReLU epilogue (mlp_engine.hpp's plain network pass, not the pipelined ladder), softplus.
+// The specular value of a row is the same bits as that kernel's.
 //
 // Dataflow.  4 waves per workgroup, one per SIMD, network loaded once (138 KiB).  Wave 0 then COMPACTS the lights: the
 // indices and positions of the lights with a non-zero weight, ascending, go to LDS (<= 14 KiB); dark lights cost nothing
@@ -19,113 +19,19 @@
 // accumulators; the pair is stored when the queue moves on to the next one.  A pair's value depends on its own tiles, in
 // their order, and on nothing else in the launch: bit-reproducible at any batch size and grid.
 // A pair without a lit front-facing light stores 0.0.
-#include "geom.hpp"
-#include "mlp128_layout.hpp"
-#include "mlp_engine.hpp"
+#include "brdf_row.hpp"
+#include "mlp128_resident.hpp"
 #include "launchers.hpp"
 
 namespace nfx {
 namespace sph {
 
 constexpr int kNW = 4, kCT = 4, kMaxLights = 1024;
-constexpr int kLdsNet = m128::kMainWeightBytes + m128::kMainBiasFloats * 4;
+using res128::kLdsNet;
+using res128::frag_off;
 constexpr int kLdsLx = kLdsNet, kLdsIdx = kLdsLx + kMaxLights * 12, kLdsCount = kLdsIdx + kMaxLights * 2;
 constexpr int kLds = kLdsCount + 16;
 static_assert(kLds <= 160 * 1024, "LDS");
-// fragment offset of chunk K: L0 0-3 (4 frags), L1 4-7, L2 8-11 (8 frags), L3 12-15 (12 frags), out 16
-constexpr int frag_off(int k) { return k < 4 ? 4 * k : k < 12 ? 16 + 8 * (k - 4) : k < 16 ? 80 + 12 * (k - 12) : 128; }
-
-// ---- closed-form row geometry: statement for statement lvis_v2.hip's (acos_poly .. brdf_row_angles)
-__device__ __forceinline__ float acos_poly(float x) {   // Abramowitz-Stegun 4.4.46, |err| <= 2e-8 + fp32 rounding
-    const float ax = fabsf(x);
-    float p = -0.0012624911f;
-    p = fmaf(p, ax, 0.0066700901f);
-    p = fmaf(p, ax, -0.0170881256f);
-    p = fmaf(p, ax, 0.0308918810f);
-    p = fmaf(p, ax, -0.0501743046f);
-    p = fmaf(p, ax, 0.0889789874f);
-    p = fmaf(p, ax, -0.2145988016f);
-    p = fmaf(p, ax, 1.5707963050f);
-    const float r = sqrtf(1.0f - ax) * p;
-    return x < 0.0f ? 3.14159265358979323846f - r : r;
-}
-__device__ __forceinline__ float atan2_poly(float y, float x) {   // Cephes atanf polynomial, |err| <= 3e-7
-    const float ax = fabsf(x), ay = fabsf(y);
-    const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
-    float t = mx > 0.0f ? mn * __builtin_amdgcn_rcpf(mx) : 0.0f;
-    const bool big = t > 0.4142135623730950f;
-    const float t2 = big ? (t - 1.0f) * __builtin_amdgcn_rcpf(t + 1.0f) : t;
-    const float zz = t2 * t2;
-    float q = fmaf(8.05374449538e-2f, zz, -1.38776856032e-1f);
-    q = fmaf(q, zz, 1.99777106478e-1f);
-    q = fmaf(q, zz, -3.33329491539e-1f);
-    float r = fmaf(q * zz, t2, t2) + (big ? 0.78539816339744830962f : 0.0f);
-    r = ay > ax ? 1.57079632679489661923f - r : r;
-    r = x < 0.0f ? 3.14159265358979323846f - r : r;
-    return y < 0.0f ? -r : r;
-}
-__device__ __forceinline__ void nrm_rsq(float (&v)[3]) {
-    const float inv = __builtin_amdgcn_rsqf(fmaxf(dot3(v, v), 1e-6f));
-    v[0] *= inv; v[1] *= inv; v[2] *= inv;
-}
-// per pair: local frame [t; b; n] of the normal and the view direction in it
-__device__ __forceinline__ void brdf_point_frame(const float (&x)[3], const float (&cm)[3], const float (&nr)[3],
-                                                 float (&rot)[9], float (&vl)[3]) {
-    float vdir[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) vdir[k] = cm[k] - x[k];
-    nrm_rsq(vdir);
-    float n[3] = {nr[0], nr[1], nr[2]}, t[3], b[3];
-    nrm_rsq(n);
-    const float zax[3] = {0.0f + 1e-6f, 0.0f + 1e-6f, 1.0f + 1e-6f};   // geom.py:128
-    cross3(n, zax, t);
-    nrm_rsq(t);
-    cross3(n, t, b);
-    nrm_rsq(b);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        rot[k] = t[k];
-        rot[3 + k] = b[k];
-        rot[6 + k] = n[k];
-    }
-    mat3_apply(rot, vdir, vl);
-    nrm_rsq(vl);
-}
-// per row: S[q] is input slot q of lane half 0 (sines, phi_d, theta_h), C[q] of half 1 (cosines, theta_d; slot 7 is z_0)
-__device__ __forceinline__ void brdf_row_angles(const float (&x)[3], const float (&lp)[3], const float (&rot)[9],
-                                                const float (&vl)[3], float (&S)[8], float (&C)[8]) {
-    auto nrm = [](float (&v)[3]) { nrm_rsq(v); };
-    float ldir[3], ll[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) ldir[k] = lp[k] - x[k];
-    nrm(ldir);
-    mat3_apply(rot, ldir, ll);
-    nrm(ll);
-    float hv[3] = {(ll[0] + vl[0]) * 0.5f, (ll[1] + vl[1]) * 0.5f, (ll[2] + vl[2]) * 0.5f};
-    nrm(hv);
-    const float cth = fminf(fmaxf(hv[2], -1.0f), 1.0f);
-    const float sxy = sqrtf(hv[0] * hv[0] + hv[1] * hv[1]);
-    const float inv = sxy > 0.0f ? __builtin_amdgcn_rcpf(sxy) : 0.0f;
-    const float cph = sxy > 0.0f ? hv[0] * inv : 1.0f, sph = hv[1] * inv;
-    const float t0 = vl[0] * cph + vl[1] * sph, t1 = vl[1] * cph - vl[0] * sph;
-    const float d0 = t0 * cth - vl[2] * sxy, d1 = t1, d2 = vl[2] * cth + t0 * sxy;
-    const float ctd = fminf(fmaxf(d2, -1.0f), 1.0f);
-    const float rxy = sqrtf(d0 * d0 + d1 * d1);
-    const float theta_h = acos_poly(cth), theta_d = acos_poly(ctd);
-    const float pi = 3.14159265358979323846f;
-    float phi_d = atan2_poly(d1, d0);
-    phi_d = phi_d - floorf(phi_d / pi) * pi;
-    const float rinv = rxy > 0.0f ? __builtin_amdgcn_rcpf(rxy) : 0.0f;
-    const bool flip = d1 < 0.0f || (d1 == 0.0f && d0 < 0.0f);
-    const float cpd0 = rxy > 0.0f ? d0 * rinv : 1.0f, spd0 = d1 * rinv;
-    const float cpd = flip ? -cpd0 : cpd0, spd = flip ? -spd0 : spd0;
-    S[0] = spd; S[1] = sxy; S[2] = rxy;
-    S[3] = 2.0f * spd * cpd; S[4] = 2.0f * sxy * cth; S[5] = 2.0f * rxy * ctd;
-    S[6] = phi_d; S[7] = theta_h;
-    C[0] = cpd; C[1] = cth; C[2] = ctd;
-    C[3] = cpd * cpd - spd * spd; C[4] = cth * cth - sxy * sxy; C[5] = ctd * ctd - rxy * rxy;
-    C[6] = theta_d; C[7] = 0.0f;
-}
 
 struct Args {
     const float* xyz;      // [n,3] sphere samples
@@ -254,7 +160,7 @@ __global__ __launch_bounds__(kNW * 64, kNW / 4) void brdf_sphere_kernel(Args a) 
                 if (h) v[7] = zv[0];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) v[8 + j] = h ? zv[2 + 2 * j] : zv[1 + 2 * j];
-#pragma unroll
+                #pragma unroll
                 for (int s = 0; s < 2; ++s)
 #pragma unroll
                     for (int j = 0; j < 8; ++j) pl[s][c][j] = (__bf16)v[8 * s + j];

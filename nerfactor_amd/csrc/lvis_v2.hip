@@ -9,148 +9,23 @@
 // MODE 0 = light visibility, MODE 1 = learned BRDF (same chunk geometry: 2 input k-steps, skip into layer 3; biases
 // instead of per-point pre-activations, softplus on front-lit rows).  Same blobs and arithmetic as lvis_kernel /
 // brdf_spec_kernel of mlp128.hip: bit-identical outputs.
-#include "geom.hpp"
-#include "mlp128_layout.hpp"
-#include "mlp_engine.hpp"
+// The resident network — its size and fragment offsets, the tile and the 17-tile ladder — is mlp128_resident.hpp; the
+// learned-BRDF row in front of it (both geometries, the input slots, the bf16 cast) is brdf_row.hpp.  This file is the two
+// kernels' dataflow around them.  (The one-time copy loop and brdf_compact_kernel's bf16 cast stay written out here: as
+// inlined functions they change the instruction text of the default kernels, profiles/brdf_row/code_objects.txt.)
+#include "brdf_row.hpp"
+#include "mlp128_resident.hpp"
 #include "launchers.hpp"
 
 namespace nfx {
 namespace lv2 {
 
+using namespace res128;
+
 constexpr int kNW = 4;
-constexpr int kLdsNet = m128::kMainWeightBytes + m128::kMainBiasFloats * 4;
 // MODE 0 additionally parks the per-point pre-activation rows of the wave's column tiles (CT x 1 KiB per wave), copied
 // one point tile ahead: the layer-0 / layer-3 accumulators then start from LDS like a bias, not from a global load
 constexpr int kLds = kLdsNet + kNW * 4 * 1024;
-// fragment offset of chunk K: L0 0-3 (4 frags), L1 4-7, L2 8-11 (8 frags), L3 12-15 (12 frags), out 16
-constexpr int frag_off(int k) { return k < 4 ? 4 * k : k < 12 ? 16 + 8 * (k - 4) : k < 16 ? 80 + 12 * (k - 12) : 128; }
-
-template <int CT>
-struct Acc {
-    f32x16 v[CT];
-};
-struct Pre {
-    bf16x8 a[2];  // first two A fragments of the next tile (layer 0 has only two k-steps)
-};
-
-template <bool RELU>
-__device__ __forceinline__ void cvt_pair(float v0, float v1, bf16x8& dst, int j) {
-    typedef short s2 __attribute__((ext_vector_type(2)));
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    const f2 vv = {v0, v1};
-    b2 pr = __builtin_convertvector(vv, b2);
-    if (RELU) {
-        s2 w = __builtin_bit_cast(s2, pr);
-        const s2 z = {0, 0};
-        w = __builtin_elementwise_max(w, z);
-        pr = __builtin_bit_cast(b2, w);
-    }
-    dst[j] = pr[0];
-    dst[j + 1] = pr[1];
-}
-
-template <int CT>
-struct EpiB {   // ReLU layer output -> next B operand (k-steps lo / hi), in register-pair pieces
-    const Acc<CT>& acc;
-    bf16x8 (&lo)[CT];
-    bf16x8 (&hi)[CT];
-    template <int R0, int R1>
-    __device__ __forceinline__ void run() {
-#pragma unroll
-        for (int r = R0; r < R1; r += 2)
-#pragma unroll
-            for (int c = 0; c < CT; ++c) {
-                if (r < 8) cvt_pair<true>(acc.v[c][r], acc.v[c][r + 1], lo[c], r);
-                else cvt_pair<true>(acc.v[c][r], acc.v[c][r + 1], hi[c], r - 8);
-            }
-    }
-};
-struct EpiNone {
-    template <int R0, int R1>
-    __device__ __forceinline__ void run() {}
-};
-
-// accumulator initialisers for the NEXT tile
-struct InitBias {   // broadcast LDS reads of the bias tile
-    const float* bias_tile;
-    template <int CT>
-    __device__ __forceinline__ void operator()(int lane, Acc<CT>& acc) const {
-        // one read group, the other column tiles' accumulators by register copy (accumulators are ArchVGPRs here):
-        // light-visibility kernel 17.57 -> 17.1 ms on r01 against one read group per column tile
-        const float* bt = bias_tile + 4 * (lane >> 5);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(bt + 8 * g);
-#pragma unroll
-            for (int c = 0; c < CT; ++c) {
-                acc.v[c][4 * g + 0] = v[0];
-                acc.v[c][4 * g + 1] = v[1];
-                acc.v[c][4 * g + 2] = v[2];
-                acc.v[c][4 * g + 3] = v[3];
-            }
-        }
-    }
-};
-template <int CT>
-struct InitPre {    // per-point pre-activation rows parked in the wave's LDS area (one point per column tile)
-    const float* rows;   // [CT][256] floats
-    int off;             // 32 t (+128 for layer 3)
-    __device__ __forceinline__ void operator()(int lane, Acc<CT>& acc) const {
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-            const float* bt = rows + c * 256 + off + 4 * (lane >> 5);
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(bt + 8 * g);
-                acc.v[c][4 * g + 0] = v[0];
-                acc.v[c][4 * g + 1] = v[1];
-                acc.v[c][4 * g + 2] = v[2];
-                acc.v[c][4 * g + 3] = v[3];
-            }
-        }
-    }
-};
-
-// Tile K: acc (already initialised) += W_K^T [b1 ; b2]; the previous tile's epilogue `prev` is spread over the
-// k-steps; once it is complete `init_next` fills acc_next for tile K+1; the first A fragments of chunk K1 are read
-// at the end.  No barrier: the weights never change.
-template <int K, int K1, int KS1, int KS2, int CT, int KS1A, int KS2A, typename Epi, typename Init>
-__device__ __forceinline__ void tile(const char* wlds, int lane, const bf16x8 (&b1)[KS1A][CT],
-                                     const bf16x8 (&b2)[KS2A][CT], Acc<CT>& acc, Acc<CT>& acc_next, Pre& pre,
-                                     Epi&& prev, Init&& init_next) {
-    constexpr int KS = KS1 + KS2;
-    // 16 accumulator registers of the previous tile in PIECES groups; at a layer boundary its outputs are this tile's
-    // LAST input k-steps, so the epilogue must be complete well before them: 4 pieces (done after k-step 3) for 8-10
-    // k-steps
-    constexpr int PIECES = KS >= 4 ? 4 : KS;
-    static_assert(16 % PIECES == 0 && (16 / PIECES) % 2 == 0, "pairs");
-    const char* f0 = wlds + frag_off(K) * kFragBytes + lane * 16;
-    bf16x8 abuf[4];
-    abuf[0] = pre.a[0];
-    abuf[1] = pre.a[1];
-    if constexpr (KS > 2) abuf[2] = *reinterpret_cast<const bf16x8*>(f0 + 2 * kFragBytes);
-    static_for<0, KS>([&](auto S) {
-        constexpr int s = decltype(S)::value;
-        if constexpr (s + 3 < KS) abuf[(s + 3) % 4] = *reinterpret_cast<const bf16x8*>(f0 + (s + 3) * kFragBytes);
-        const bf16x8 a = abuf[s % 4];
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-            const bf16x8 b = s < KS1 ? b1[s < KS1 ? s : 0][c] : b2[s >= KS1 ? s - KS1 : 0][c];
-            acc.v[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc.v[c], 0, 0, 0);
-        }
-        if constexpr (s < PIECES) prev.template run<16 * s / PIECES, 16 * (s + 1) / PIECES>();
-        if constexpr (s == PIECES - 1) {
-            // keep the next tile's initial loads BEHIND the epilogue that frees their destination registers (hoisted
-            // above it they need 16 CT temporaries and spill at CT = 4)
-            __builtin_amdgcn_sched_barrier(0);
-            init_next(lane, acc_next);
-        }
-    });
-    const char* f1 = wlds + frag_off(K1) * kFragBytes + lane * 16;
-    pre.a[0] = *reinterpret_cast<const bf16x8*>(f1);
-    pre.a[1] = *reinterpret_cast<const bf16x8*>(f1 + kFragBytes);
-}
 
 struct Args {
     const float* xyz;      // [n,3] points (lvis: the points the directions are taken from)
@@ -299,41 +174,19 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void resident128_kernel(Args a) {
                 pre_pt[c] = a.pre + pt * 256;
                 front[c] = true;
             } else {
-                float cm[3], nr[3], ldir[3], vdir[3], rot[9], ll[3], vl[3], rus[3];
+                float cm[3], nr[3], rus[3], v[16];
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
                     cm[k] = a.cam[pt * 3 + k];
                     nr[k] = a.normal[pt * 3 + k];
                 }
-                dir_to(lp, x, ldir);          // shape.py:128-131
-                dir_to(cm, x, vdir);          // shape.py:137-140
-                world2local(nr, rot);         // util/geom.py:119-149
-                mat3_apply(rot, ldir, ll);    // nerfactor.py:418-419
-                mat3_apply(rot, vdir, vl);
-                dir2rusink(ll, vl, rus);      // util/geom.py:152-192 with a = light, b = view
-                front[c] = ll[2] > 0.0f;      // nerfactor.py:429-432
-                // B operand slots of brdf_input_slots() (mlp128_layout.hpp)
-                float v[16];
-#pragma unroll
-                for (int q = 0; q < 6; ++q) v[q] = sin_shifted_small(rus[q % 3] * (float)(1 << (q / 3)), h);   // angles <= pi, 2 bands
-                v[6] = h ? rus[2] : rus[0];
-                v[7] = h ? a.z[pt * a.z_dim] : rus[1];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int i = 1 + 2 * j + h;
-                    v[8 + j] = i < a.z_dim ? a.z[pt * a.z_dim + i] : 0.0f;
-                }
-#pragma unroll
-                for (int sidx = 0; sidx < 2; ++sidx) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) pl[sidx][c][j] = (__bf16)v[8 * sidx + j];
-                }
+                front[c] = brdf_row_rusink(x, lp, cm, nr, rus);
+                brdf_fill_slots(rus, a.z + pt * a.z_dim, a.z_dim, h, v);
+                brdf_cast_slots(v, pl, c);
                 pre_pt[c] = nullptr;
             }
         }
-        bf16x8 ha[8][CT], hb[8][CT];
         Acc<CT> accs[2];
-        Pre pre;
         // initial accumulators of the layer-0 / layer-3 tiles: per-point pre-activations (MODE 0) or plain biases
         auto init03 = [&](int off_pre, int off_bias) {
             return [=](int ln, Acc<CT>& ac) {
@@ -341,37 +194,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void resident128_kernel(Args a) {
                 else InitBias{bias_lds + off_bias}(ln, ac);
             };
         };
-        {   // tile 0's operands
-            const char* f0 = wlds + lane * 16;
-            pre.a[0] = *reinterpret_cast<const bf16x8*>(f0);
-            pre.a[1] = *reinterpret_cast<const bf16x8*>(f0 + kFragBytes);
-            init03(0, 0)(lane, accs[0]);
-        }
-        // chunk K accumulates in accs[K & 1]; layers: L0 K 0-3 (pl -> ha), L1 4-7 (ha -> hb), L2 8-11 (hb -> ha),
-        // L3 12-15 ([ha ; pl] -> hb), out 16 (hb -> activation)
-#define NFX_LV2_TILE(K, KS1, KS2, B1, B2, PREV, NEXT) \
-        tile<K, (K + 1) % 17, KS1, KS2, CT>(wlds, lane, B1, B2, accs[(K) & 1], accs[((K) + 1) & 1], pre, PREV, NEXT)
-#define NFX_LV2_EPI(K, OUT, T) EpiB<CT>{accs[(K) & 1], OUT[2 * (T)], OUT[2 * (T) + 1]}
-        NFX_LV2_TILE(0, 2, 0, pl, pl, EpiNone{}, init03(32, 32));
-        NFX_LV2_TILE(1, 2, 0, pl, pl, NFX_LV2_EPI(0, ha, 0), init03(64, 64));
-        NFX_LV2_TILE(2, 2, 0, pl, pl, NFX_LV2_EPI(1, ha, 1), init03(96, 96));
-        NFX_LV2_TILE(3, 2, 0, pl, pl, NFX_LV2_EPI(2, ha, 2), (InitBias{bias_lds + 128}));
-        NFX_LV2_TILE(4, 8, 0, ha, pl, NFX_LV2_EPI(3, ha, 3), (InitBias{bias_lds + 128 + 32}));
-        NFX_LV2_TILE(5, 8, 0, ha, pl, NFX_LV2_EPI(4, hb, 0), (InitBias{bias_lds + 128 + 64}));
-        NFX_LV2_TILE(6, 8, 0, ha, pl, NFX_LV2_EPI(5, hb, 1), (InitBias{bias_lds + 128 + 96}));
-        NFX_LV2_TILE(7, 8, 0, ha, pl, NFX_LV2_EPI(6, hb, 2), (InitBias{bias_lds + 256}));
-        NFX_LV2_TILE(8, 8, 0, hb, pl, NFX_LV2_EPI(7, hb, 3), (InitBias{bias_lds + 256 + 32}));
-        NFX_LV2_TILE(9, 8, 0, hb, pl, NFX_LV2_EPI(8, ha, 0), (InitBias{bias_lds + 256 + 64}));
-        NFX_LV2_TILE(10, 8, 0, hb, pl, NFX_LV2_EPI(9, ha, 1), (InitBias{bias_lds + 256 + 96}));
-        NFX_LV2_TILE(11, 8, 0, hb, pl, NFX_LV2_EPI(10, ha, 2), init03(128, 384));
-        NFX_LV2_TILE(12, 8, 2, ha, pl, NFX_LV2_EPI(11, ha, 3), init03(128 + 32, 384 + 32));
-        NFX_LV2_TILE(13, 8, 2, ha, pl, NFX_LV2_EPI(12, hb, 0), init03(128 + 64, 384 + 64));
-        NFX_LV2_TILE(14, 8, 2, ha, pl, NFX_LV2_EPI(13, hb, 1), init03(128 + 96, 384 + 96));
-        NFX_LV2_TILE(15, 8, 2, ha, pl, NFX_LV2_EPI(14, hb, 2), (InitBias{bias_lds + 512}));
-        park_rows();   // the rows of THIS point tile were last read by tile 14's initialiser (LDS ops of a wave are in order)
-        NFX_LV2_TILE(16, 8, 0, hb, pl, NFX_LV2_EPI(15, hb, 3), [](int, Acc<CT>&) {});
-#undef NFX_LV2_TILE
-#undef NFX_LV2_EPI
+        // park: the rows of THIS point tile were last read by tile 14's initialiser (LDS ops of a wave are in order)
+        ladder<CT>(wlds, bias_lds, lane, pl, accs, init03, park_rows);
         if (h == 0) {
 #pragma unroll
             for (int c = 0; c < CT; ++c)
@@ -424,195 +248,11 @@ template <int NW> struct Queue {
 };
 __device__ __forceinline__ int ring_wrap(int i, int cap) { return i >= cap ? i - cap : i; }   // i < 2 cap
 
-__device__ __forceinline__ float acos_poly(float x) {   // Abramowitz-Stegun 4.4.46, |err| <= 2e-8 + fp32 rounding
-    const float ax = fabsf(x);
-    float p = -0.0012624911f;
-    p = fmaf(p, ax, 0.0066700901f);
-    p = fmaf(p, ax, -0.0170881256f);
-    p = fmaf(p, ax, 0.0308918810f);
-    p = fmaf(p, ax, -0.0501743046f);
-    p = fmaf(p, ax, 0.0889789874f);
-    p = fmaf(p, ax, -0.2145988016f);
-    p = fmaf(p, ax, 1.5707963050f);
-    const float r = sqrtf(1.0f - ax) * p;
-    return x < 0.0f ? 3.14159265358979323846f - r : r;
-}
-__device__ __forceinline__ float atan2_poly(float y, float x) {   // Cephes atanf polynomial, |err| <= 3e-7
-    const float ax = fabsf(x), ay = fabsf(y);
-    const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
-    float t = mx > 0.0f ? mn * __builtin_amdgcn_rcpf(mx) : 0.0f;
-    const bool big = t > 0.4142135623730950f;
-    const float t2 = big ? (t - 1.0f) * __builtin_amdgcn_rcpf(t + 1.0f) : t;
-    const float zz = t2 * t2;
-    float q = fmaf(8.05374449538e-2f, zz, -1.38776856032e-1f);
-    q = fmaf(q, zz, 1.99777106478e-1f);
-    q = fmaf(q, zz, -3.33329491539e-1f);
-    float r = fmaf(q * zz, t2, t2) + (big ? 0.78539816339744830962f : 0.0f);
-    r = ay > ax ? 1.57079632679489661923f - r : r;
-    r = x < 0.0f ? 3.14159265358979323846f - r : r;
-    return y < 0.0f ? -r : r;
-}
-
-// B-operand values (slot order of brdf_input_slots(), mlp128_layout.hpp) of one (point, light) row, lane half h
-template <int GEO>
-__device__ __forceinline__ void brdf_row_inputs(const float (&x)[3], const float (&lp)[3], const float (&cm)[3],
-                                                const float (&nr)[3], const float* zp, int z_dim, int h,
-                                                float (&v)[16]) {
-    float ldir[3], vdir[3], rot[9], ll[3], vl[3];
-    if constexpr (GEO == 0) {
-        dir_to(lp, x, ldir);          // shape.py:128-131
-        dir_to(cm, x, vdir);          // shape.py:137-140
-        world2local(nr, rot);         // util/geom.py:119-149
-    } else {
-        // same formulas with v_rsq_f32 (1 ulp) instead of the IEEE sqrt + divide sequences (~22 instructions per
-        // normalisation, eight of them per row, executed at dependent-issue latency by a lone wave)
-        auto nrm = [](float (&v)[3]) {
-            const float inv = __builtin_amdgcn_rsqf(fmaxf(dot3(v, v), 1e-6f));
-            v[0] *= inv; v[1] *= inv; v[2] *= inv;
-        };
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            ldir[k] = lp[k] - x[k];
-            vdir[k] = cm[k] - x[k];
-        }
-        nrm(ldir);
-        nrm(vdir);
-        float n[3] = {nr[0], nr[1], nr[2]}, t[3], b[3];
-        nrm(n);
-        const float zax[3] = {0.0f + 1e-6f, 0.0f + 1e-6f, 1.0f + 1e-6f};   // geom.py:128
-        cross3(n, zax, t);
-        nrm(t);
-        cross3(n, t, b);
-        nrm(b);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            rot[k] = t[k];
-            rot[3 + k] = b[k];
-            rot[6 + k] = n[k];
-        }
-    }
-    mat3_apply(rot, ldir, ll);    // nerfactor.py:418-419
-    mat3_apply(rot, vdir, vl);
-    if constexpr (GEO == 0) {
-        float rus[3];
-        dir2rusink(ll, vl, rus);  // util/geom.py:152-192 with a = light, b = view
-#pragma unroll
-        for (int q = 0; q < 6; ++q) v[q] = sin_shifted_small(rus[q % 3] * (float)(1 << (q / 3)), h);
-        v[6] = h ? rus[2] : rus[0];
-        v[7] = h ? zp[0] : rus[1];
-    } else {
-        auto nrm = [](float (&v)[3]) {
-            const float inv = __builtin_amdgcn_rsqf(fmaxf(dot3(v, v), 1e-6f));
-            v[0] *= inv; v[1] *= inv; v[2] *= inv;
-        };
-        nrm(ll);                  // dir2rusink re-normalises its inputs (geom.py:158-159)
-        nrm(vl);
-        float hv[3] = {(ll[0] + vl[0]) * 0.5f, (ll[1] + vl[1]) * 0.5f, (ll[2] + vl[2]) * 0.5f};
-        nrm(hv);
-        const float cth = fminf(fmaxf(hv[2], -1.0f), 1.0f);
-        const float sxy = sqrtf(hv[0] * hv[0] + hv[1] * hv[1]);           // sin(theta_h) >= 0
-        const float inv = sxy > 0.0f ? __builtin_amdgcn_rcpf(sxy) : 0.0f;
-        const float cph = sxy > 0.0f ? hv[0] * inv : 1.0f, sph = hv[1] * inv;   // atan2(0, 0) = 0
-        // diff = R_y(-theta_h) R_z(-phi_h) b with b = view (geom.py:183)
-        const float t0 = vl[0] * cph + vl[1] * sph, t1 = vl[1] * cph - vl[0] * sph;
-        const float d0 = t0 * cth - vl[2] * sxy, d1 = t1, d2 = vl[2] * cth + t0 * sxy;
-        const float ctd = fminf(fmaxf(d2, -1.0f), 1.0f);
-        const float rxy = sqrtf(d0 * d0 + d1 * d1);                       // sin(theta_d) >= 0
-        const float theta_h = acos_poly(cth), theta_d = acos_poly(ctd);
-        const float pi = 3.14159265358979323846f;
-        float phi_d = atan2_poly(d1, d0);
-        phi_d = phi_d - floorf(phi_d / pi) * pi;                          // tf.math.floormod(x, pi)
-        const float rinv = rxy > 0.0f ? __builtin_amdgcn_rcpf(rxy) : 0.0f;
-        const bool flip = d1 < 0.0f || (d1 == 0.0f && d0 < 0.0f);        // + pi: both signs change
-        const float cpd0 = rxy > 0.0f ? d0 * rinv : 1.0f, spd0 = d1 * rinv;
-        const float cpd = flip ? -cpd0 : cpd0, spd = flip ? -spd0 : spd0;
-        // band 0: (phi_d, theta_h, theta_d), band 1: the doubled angles
-        if (h == 0) {
-            v[0] = spd; v[1] = sxy; v[2] = rxy;
-            v[3] = 2.0f * spd * cpd; v[4] = 2.0f * sxy * cth; v[5] = 2.0f * rxy * ctd;
-        } else {
-            v[0] = cpd; v[1] = cth; v[2] = ctd;
-            v[3] = cpd * cpd - spd * spd; v[4] = cth * cth - sxy * sxy; v[5] = ctd * ctd - rxy * rxy;
-        }
-        v[6] = h ? theta_d : phi_d;
-        v[7] = h ? zp[0] : theta_h;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int i = 1 + 2 * j + h;
-        v[8 + j] = i < z_dim ? zp[i] : 0.0f;
-    }
-}
-
-// The closed-form geometry of ONE (point, light) row (brdf_point_frame + brdf_row_angles) with the values of BOTH lane halves: S[q] is what the half-0 lane
-// of the row's column puts into input slot q (sines, phi_d, theta_h), C[q] what the half-1 lane does (cosines, theta_d;
-// slot 7 of half 1 is z_0, loaded by the caller).  brdf_compact_kernel lets the half-0 lane of column p compute the row
-// of column tile 2k and the half-1 lane the row of tile 2k + 1, and swaps halves (one exchange per slot): each lane
-// runs the geometry of CT / 2 rows instead of CT (the two halves used to compute the same row twice).
-__device__ __forceinline__ void nrm_rsq(float (&v)[3]) {
-    const float inv = __builtin_amdgcn_rsqf(fmaxf(dot3(v, v), 1e-6f));
-    v[0] *= inv; v[1] *= inv; v[2] *= inv;
-}
-// The per-POINT half of the row geometry: local frame [t; b; n] of the normal and the view direction in it.  The queue
-// fill computes it once per point and parks it in LDS (r03); brdf_row_angles is what is left per (point, light) row.
-// Same operations in the same order as the per-row form of round 2: the rows come out bit-identical.
-__device__ __forceinline__ void brdf_point_frame(const float (&x)[3], const float (&cm)[3], const float (&nr)[3],
-                                                 float (&rot)[9], float (&vl)[3]) {
-    float vdir[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) vdir[k] = cm[k] - x[k];
-    nrm_rsq(vdir);
-    float n[3] = {nr[0], nr[1], nr[2]}, t[3], b[3];
-    nrm_rsq(n);
-    const float zax[3] = {0.0f + 1e-6f, 0.0f + 1e-6f, 1.0f + 1e-6f};   // geom.py:128
-    cross3(n, zax, t);
-    nrm_rsq(t);
-    cross3(n, t, b);
-    nrm_rsq(b);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        rot[k] = t[k];
-        rot[3 + k] = b[k];
-        rot[6 + k] = n[k];
-    }
-    mat3_apply(rot, vdir, vl);
-    nrm_rsq(vl);
-}
-__device__ __forceinline__ void brdf_row_angles(const float (&x)[3], const float (&lp)[3], const float (&rot)[9],
-                                                const float (&vl)[3], float (&S)[8], float (&C)[8]) {
-    auto nrm = [](float (&v)[3]) { nrm_rsq(v); };
-    float ldir[3], ll[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) ldir[k] = lp[k] - x[k];
-    nrm(ldir);
-    mat3_apply(rot, ldir, ll);
-    nrm(ll);
-    float hv[3] = {(ll[0] + vl[0]) * 0.5f, (ll[1] + vl[1]) * 0.5f, (ll[2] + vl[2]) * 0.5f};
-    nrm(hv);
-    const float cth = fminf(fmaxf(hv[2], -1.0f), 1.0f);
-    const float sxy = sqrtf(hv[0] * hv[0] + hv[1] * hv[1]);
-    const float inv = sxy > 0.0f ? __builtin_amdgcn_rcpf(sxy) : 0.0f;
-    const float cph = sxy > 0.0f ? hv[0] * inv : 1.0f, sph = hv[1] * inv;
-    const float t0 = vl[0] * cph + vl[1] * sph, t1 = vl[1] * cph - vl[0] * sph;
-    const float d0 = t0 * cth - vl[2] * sxy, d1 = t1, d2 = vl[2] * cth + t0 * sxy;
-    const float ctd = fminf(fmaxf(d2, -1.0f), 1.0f);
-    const float rxy = sqrtf(d0 * d0 + d1 * d1);
-    const float theta_h = acos_poly(cth), theta_d = acos_poly(ctd);
-    const float pi = 3.14159265358979323846f;
-    float phi_d = atan2_poly(d1, d0);
-    phi_d = phi_d - floorf(phi_d / pi) * pi;
-    const float rinv = rxy > 0.0f ? __builtin_amdgcn_rcpf(rxy) : 0.0f;
-    const bool flip = d1 < 0.0f || (d1 == 0.0f && d0 < 0.0f);
-    const float cpd0 = rxy > 0.0f ? d0 * rinv : 1.0f, spd0 = d1 * rinv;
-    const float cpd = flip ? -cpd0 : cpd0, spd = flip ? -spd0 : spd0;
-    S[0] = spd; S[1] = sxy; S[2] = rxy;
-    S[3] = 2.0f * spd * cpd; S[4] = 2.0f * sxy * cth; S[5] = 2.0f * rxy * ctd;
-    S[6] = phi_d; S[7] = theta_h;
-    C[0] = cpd; C[1] = cth; C[2] = ctd;
-    C[3] = cpd * cpd - spd * spd; C[4] = cth * cth - sxy * sxy; C[5] = ctd * ctd - rxy * rxy;
-    C[6] = theta_d; C[7] = 0.0f;
-}
-
+// The rows' values come from brdf_row.hpp.  brdf_compact_kernel lets the half-0 lane of column p compute the closed-form row
+// (brdf_row_angles: the values of BOTH lane halves) of column tile 2k and the half-1 lane the row of tile 2k + 1, and swaps
+// halves (one exchange per slot): each lane runs the geometry of CT / 2 rows instead of CT (the two halves used to compute
+// the same row twice).  The per-POINT half (brdf_point_frame) is computed once per point by the queue fill and parked in LDS.
+//
 // NW = 8, CT = 2 (default since r03): two waves per SIMD — one wave's queue fill and Rusinkiewicz VALU run under its
 //   partner's MFMAs.  NW = 4 (CT = 2 | 3 | 4): one wave per SIMD, the shipped form of round 2.
 // Round 2 measured the 8-wave form faster but NOT deterministic (a few thousand of 10^8 rows wrong, in groups of 16
@@ -812,39 +452,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void brdf_compact_kernel(Args a) {
                 }
             }
         }
-        bf16x8 ha[8][CT], hb[8][CT];
         Acc<CT> accs[2];
-        Pre pre;
-        {
-            const char* f0 = wlds + lane * 16;
-            pre.a[0] = *reinterpret_cast<const bf16x8*>(f0);
-            pre.a[1] = *reinterpret_cast<const bf16x8*>(f0 + kFragBytes);
-            InitBias{bias_lds}(lane, accs[0]);
-        }
-#define NFX_LV3_TILE(K, KS1, KS2, B1, B2, PREV, NEXT) \
-        tile<K, (K + 1) % 17, KS1, KS2, CT>(wlds, lane, B1, B2, accs[(K) & 1], accs[((K) + 1) & 1], pre, PREV, NEXT)
-#define NFX_LV3_EPI(K, OUT, T) EpiB<CT>{accs[(K) & 1], OUT[2 * (T)], OUT[2 * (T) + 1]}
-#define NFX_LV3_BIAS(OFF) (InitBias{bias_lds + (OFF)})
-        NFX_LV3_TILE(0, 2, 0, pl, pl, EpiNone{}, NFX_LV3_BIAS(32));
-        NFX_LV3_TILE(1, 2, 0, pl, pl, NFX_LV3_EPI(0, ha, 0), NFX_LV3_BIAS(64));
-        NFX_LV3_TILE(2, 2, 0, pl, pl, NFX_LV3_EPI(1, ha, 1), NFX_LV3_BIAS(96));
-        NFX_LV3_TILE(3, 2, 0, pl, pl, NFX_LV3_EPI(2, ha, 2), NFX_LV3_BIAS(128));
-        NFX_LV3_TILE(4, 8, 0, ha, pl, NFX_LV3_EPI(3, ha, 3), NFX_LV3_BIAS(128 + 32));
-        NFX_LV3_TILE(5, 8, 0, ha, pl, NFX_LV3_EPI(4, hb, 0), NFX_LV3_BIAS(128 + 64));
-        NFX_LV3_TILE(6, 8, 0, ha, pl, NFX_LV3_EPI(5, hb, 1), NFX_LV3_BIAS(128 + 96));
-        NFX_LV3_TILE(7, 8, 0, ha, pl, NFX_LV3_EPI(6, hb, 2), NFX_LV3_BIAS(256));
-        NFX_LV3_TILE(8, 8, 0, hb, pl, NFX_LV3_EPI(7, hb, 3), NFX_LV3_BIAS(256 + 32));
-        NFX_LV3_TILE(9, 8, 0, hb, pl, NFX_LV3_EPI(8, ha, 0), NFX_LV3_BIAS(256 + 64));
-        NFX_LV3_TILE(10, 8, 0, hb, pl, NFX_LV3_EPI(9, ha, 1), NFX_LV3_BIAS(256 + 96));
-        NFX_LV3_TILE(11, 8, 0, hb, pl, NFX_LV3_EPI(10, ha, 2), NFX_LV3_BIAS(384));
-        NFX_LV3_TILE(12, 8, 2, ha, pl, NFX_LV3_EPI(11, ha, 3), NFX_LV3_BIAS(384 + 32));
-        NFX_LV3_TILE(13, 8, 2, ha, pl, NFX_LV3_EPI(12, hb, 0), NFX_LV3_BIAS(384 + 64));
-        NFX_LV3_TILE(14, 8, 2, ha, pl, NFX_LV3_EPI(13, hb, 1), NFX_LV3_BIAS(384 + 96));
-        NFX_LV3_TILE(15, 8, 2, ha, pl, NFX_LV3_EPI(14, hb, 2), NFX_LV3_BIAS(512));
-        NFX_LV3_TILE(16, 8, 0, hb, pl, NFX_LV3_EPI(15, hb, 3), [](int, Acc<CT>&) {});
-#undef NFX_LV3_TILE
-#undef NFX_LV3_EPI
-#undef NFX_LV3_BIAS
+        ladder<CT>(wlds, bias_lds, lane, pl, accs, [&](int, int off_bias) { return InitBias{bias_lds + off_bias}; }, [] {});
         if (h == 0) {
 #pragma unroll
             for (int c = 0; c < CT; ++c)

@@ -4,7 +4,7 @@
 //   lvis_pre + lvis   _pred_lvis_at over the light sphere             shape.py:213-237 (+128-135)
 //   brdf_spec    learned-BRDF specular term of _eval_brdf_at          nerfactor.py:413-458,
 //                                                                     util/geom.py:119-192
-#include "geom.hpp"
+#include "brdf_row.hpp"
 #include "mlp128_layout.hpp"
 #include "mlp_engine.hpp"
 #include "launchers.hpp"
@@ -171,10 +171,7 @@ __global__ __launch_bounds__(kNW * 64, 2) void lvis_kernel(
 }
 
 // ---------------------------------------------------------------------------------------
-// brdf_spec: rows (n, l).  Input slots (k-step s, half h, element j), see brdf_input_slots():
-//   s=0: h=0: sin(r0) sin(r1) sin(r2) sin(2r0) sin(2r1) sin(2r2) r0 r1
-//        h=1: cos(r0) ...                         cos(2r2)       r2 z0
-//   s=1: z_i (i >= 1) at h = (i-1)&1, j = (i-1)>>1; zero elsewhere
+// brdf_spec: rows (n, l) in the reference's op order; the row and its input slots are brdf_row.hpp
 __global__ __launch_bounds__(kNW * 64, 2) void brdf_spec_kernel(
     const float* __restrict__ xyz, const float* __restrict__ cam, const float* __restrict__ normal,
     const float* __restrict__ z, int z_dim, const float* __restrict__ lxyz, int n_lights,
@@ -209,31 +206,11 @@ __global__ __launch_bounds__(kNW * 64, 2) void brdf_spec_kernel(
             nr[k] = normal[pt * 3 + k];
             lp[k] = lxyz[l * 3 + k];
         }
-        float ldir[3], vdir[3], rot[9], ll[3], vl[3], rus[3];
-        dir_to(lp, x, ldir);          // shape.py:128-131
-        dir_to(c, x, vdir);           // shape.py:137-140
-        world2local(nr, rot);         // util/geom.py:119-149
-        mat3_apply(rot, ldir, ll);    // nerfactor.py:418-419
-        mat3_apply(rot, vdir, vl);
-        dir2rusink(ll, vl, rus);      // util/geom.py:152-192 with a = light, b = view
-        const bool front = ll[2] > 0.0f;  // nerfactor.py:429-432
-        // B operand
-        float v[16];
-#pragma unroll
-        for (int q = 0; q < 6; ++q) v[q] = sin_shifted_small(rus[q % 3] * (float)(1 << (q / 3)), h);   // angles <= pi, 2 bands
-        v[6] = h ? rus[2] : rus[0];
-        v[7] = h ? z[pt * z_dim] : rus[1];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int i = 1 + 2 * j + h;  // z index held by (half h, element j) of k-step 1
-            v[8 + j] = i < z_dim ? z[pt * z_dim + i] : 0.0f;
-        }
+        float rus[3], v[16];
+        const bool front = brdf_row_rusink(x, lp, c, nr, rus);
+        brdf_fill_slots(rus, z + pt * z_dim, z_dim, h, v);
         bf16x8 bin[2][1], ha[8][1], hb[8][1];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) bin[s][0][j] = (__bf16)v[8 * s + j];
-        }
+        brdf_cast_slots(v, bin, 0);
         layer<2, 0, 4, kNL0, kNLH, true, kNW>(ws, tid, bias_lds, bin, bin, ha);
         mid_layers<kNL3>(ws, tid, bias_lds, ha, hb, bin);
         layer<8, 2, 4, kNL3, kNLOut, true, kNW>(ws, tid, bias_lds + 384, ha, bin, hb);

@@ -8,7 +8,7 @@
 //   NFX_IN_XYZ_LDIR  8 (6 used) 8         16 (8 + 6 used)    8      168
 //   NFX_IN_Z_RUSINK  4 (2 used) 8         12 (8 + 2 used)    8      136
 // (reference: shape.py:184-237, nerfactor.py:377-461 — the reference computes all of this in fp32).
-#include "geom.hpp"
+#include "brdf_row.hpp"
 #include "mlp128_layout.hpp"
 #include "mlp_x3.hpp"
 #include "launchers.hpp"
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(kNW * 64, 1) void mlp128_x3_kernel(Args a) {
                 xin[5] = pl[1];
             }
         } else {
-            float x[3], lp[3], cm[3], nr[3], ldir[3], vdir[3], rot[9], ll[3], vl[3], rus[3];
+            float x[3], lp[3], cm[3], nr[3], rus[3], v[16];
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 x[k] = a.xyz[pt * 3 + k];
@@ -121,24 +121,8 @@ __global__ __launch_bounds__(kNW * 64, 1) void mlp128_x3_kernel(Args a) {
                 cm[k] = a.cam[pt * 3 + k];
                 nr[k] = a.normal[pt * 3 + k];
             }
-            dir_to(lp, x, ldir);          // shape.py:128-131
-            dir_to(cm, x, vdir);          // shape.py:137-140
-            world2local(nr, rot);         // util/geom.py:119-149
-            mat3_apply(rot, ldir, ll);    // nerfactor.py:418-419
-            mat3_apply(rot, vdir, vl);
-            dir2rusink(ll, vl, rus);      // util/geom.py:152-192
-            front = ll[2] > 0.0f;         // nerfactor.py:429-432
-            const float* zp = a.z + pt * a.z_dim;
-            float v[16];
-#pragma unroll
-            for (int q = 0; q < 6; ++q) v[q] = sin_shifted(rus[q % 3] * (float)(1 << (q / 3)), h);
-            v[6] = h ? rus[2] : rus[0];
-            v[7] = h ? zp[0] : rus[1];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int i = 1 + 2 * j + h;
-                v[8 + j] = i < a.z_dim ? zp[i] : 0.0f;
-            }
+            front = brdf_row_rusink(x, lp, cm, nr, rus);
+            brdf_fill_slots<false>(rus, a.z + pt * a.z_dim, a.z_dim, h, v);   // full-range sine
             Pair pr[2];
             to_pairs(v, pr);
             xin[0] = pr[0];

@@ -1,9 +1,14 @@
-"""Outputs of the density / density-gradient kernels (nerf_geom.hip, nerf_geom_x3.hip, nerf_sigma_x3_pipe.hip) and the bytes
-of the fp32-class packers, saved (first call) or compared bit for bit (later calls): the check for a change of these sources
+"""Outputs of kernels, saved (first call) or compared bit for bit (later calls): the check for a change of their sources
 that must not change a single bit.  One process per library:
     NFX_LIB_PATH=old.so python scripts/geom_identity.py save;  python scripts/geom_identity.py check
     ... save --pack-only / check --pack-only: the packers alone (no GPU)
-The 840-point sets of tests/nerf_point_cases.py ('glorot', 'fitted'), as [8, 105] and [120, 7]."""
+    ... save --group rows / check --group rows: the second group of cases
+--group geom (the default): the density / density-gradient kernels (nerf_geom.hip, nerf_geom_x3.hip, nerf_sigma_x3_pipe.hip)
+  and the bytes of the fp32-class packers, on the 840-point sets of tests/nerf_point_cases.py ('glorot', 'fitted'), as
+  [8, 105] and [120, 7].
+--group rows: the width-128 row kernels behind brdf_row.hpp and mlp128_resident.hpp (lvis_v2.hip, mlp128.hip, mlp128_x3.hip,
+  brdf_sphere.hip, brdf_bwd.hip) on the seeded cases of tests/row_mlp_cases.py, tests/test_gpu_brdf_sphere.py and
+  tests/bwd_probes.py."""
 import hashlib
 import os
 import sys
@@ -22,7 +27,9 @@ from tests import common, nerf_point_cases as pc  # noqa: E402
 
 mode = sys.argv[1]
 pack_only = '--pack-only' in sys.argv
-path = os.path.join(ROOT, 'build', 'geom_identity_pack.pt' if pack_only else 'geom_identity.pt')     # build/ is not tracked
+group = sys.argv[sys.argv.index('--group') + 1] if '--group' in sys.argv else 'geom'
+assert group in ('geom', 'rows') and not (pack_only and group == 'rows')
+path = os.path.join(ROOT, 'build', 'geom_identity_pack.pt' if pack_only else 'geom_identity.pt' if group == 'geom' else 'geom_identity_rows.pt')     # build/ is not tracked
 out = {}
 
 
@@ -34,53 +41,118 @@ def option(key, value, fn):
         _capi.unset_option(key)
 
 
-# ------------------------------------------------------------------------------------------ the packers' bytes, prec = 'fp32'
-for name in pc.SETS:
-    ks, bs = common.nerf_layers(pc.point_set(name).net)
-    out['pack_nerf_weights/' + name] = ops.pack_nerf_weights(ks, bs, 'fp32')
-    out['pack_nerf_geom_weights/' + name] = ops.pack_nerf_geom_weights(ks, bs, 'fp32')
-rng = np.random.default_rng(128)
-for in_kind, z_dim, out_dim in ((_capi.IN_XYZ, 0, 3), (_capi.IN_XYZ_LDIR, 0, 1), (_capi.IN_Z_RUSINK, 3, 1)):
-    in_dims = {_capi.IN_XYZ: 63, _capi.IN_XYZ_LDIR: 90, _capi.IN_Z_RUSINK: z_dim + 15}[in_kind]
-    shapes = [(in_dims, 128), (128, 128), (128, 128), (128 + in_dims, 128), (128, out_dim)]
-    ks = [rng.normal(size=s).astype(np.float32) / np.sqrt(s[0]) for s in shapes]
-    bs = [rng.normal(size=s[1]).astype(np.float32) * .1 for s in shapes]
-    out['pack_mlp128_weights/%d_%d_%d' % (in_kind, z_dim, out_dim)] = ops.pack_mlp128_weights(ks, bs, in_kind, out_dim, z_dim, 'fp32')
-
-# ------------------------------------------------------------------------------------------------------------- the kernels
-if not pack_only:
-    dev = torch.device('cuda:0')
+def geom_cases():
+    # ------------------------------------------------------------------------------------------ the packers' bytes, prec = 'fp32'
     for name in pc.SETS:
-        ps = pc.point_set(name)
-        blob = {p: ops.pack_nerf_geom_weights(*common.nerf_layers(ps.net), prec=p).to(dev) for p in ('bf16', 'fp32')}
-        picked = np.random.default_rng(840).permutation(pc.N)[:333].astype(np.int32)
-        lst = torch.full((pc.N,), -1, dtype=torch.int32, device=dev)
-        lst[:333] = torch.from_numpy(picked).to(dev)
-        cnt = torch.tensor([333], dtype=torch.int32, device=dev)
-        for s in (105, 7):
-            o, d, z = (torch.from_numpy(np.array(a)).to(dev) for a in ps.layout(s))
-            n = pc.N // s
-            key = '%s/S%d/' % (name, s)
-            for v in (0, 1):
-                out[key + 'sigma_fwd bf16 sigma_variant %d' % v] = option('sigma_variant', v, lambda: ops.nerf_sigma_fwd(o, d, z, blob['bf16'], 'bf16'))
-                out[key + 'sigma_fwd fp32 sigma_x3_variant %d' % v] = option('sigma_x3_variant', v, lambda: ops.nerf_sigma_fwd(o, d, z, blob['fp32'], 'fp32'))
-                for p in ('bf16', 'fp32'):
-                    nrm, sig = option('sigma_grad_rows', v, lambda: ops.nerf_sigma_grad(o, d, z, blob[p], p))
-                    out[key + 'sigma_grad %s sigma_grad_rows %d' % (p, v)] = torch.cat([nrm, sig[..., None]], -1)
+        ks, bs = common.nerf_layers(pc.point_set(name).net)
+        out['pack_nerf_weights/' + name] = ops.pack_nerf_weights(ks, bs, 'fp32')
+        out['pack_nerf_geom_weights/' + name] = ops.pack_nerf_geom_weights(ks, bs, 'fp32')
+    rng = np.random.default_rng(128)
+    for in_kind, z_dim, out_dim in ((_capi.IN_XYZ, 0, 3), (_capi.IN_XYZ_LDIR, 0, 1), (_capi.IN_Z_RUSINK, 3, 1)):
+        in_dims = {_capi.IN_XYZ: 63, _capi.IN_XYZ_LDIR: 90, _capi.IN_Z_RUSINK: z_dim + 15}[in_kind]
+        shapes = [(in_dims, 128), (128, 128), (128, 128), (128 + in_dims, 128), (128, out_dim)]
+        ks = [rng.normal(size=s).astype(np.float32) / np.sqrt(s[0]) for s in shapes]
+        bs = [rng.normal(size=s[1]).astype(np.float32) * .1 for s in shapes]
+        out['pack_mlp128_weights/%d_%d_%d' % (in_kind, z_dim, out_dim)] = ops.pack_mlp128_weights(ks, bs, in_kind, out_dim, z_dim, 'fp32')
 
-                def stride4():
-                    rgbs = torch.full((n, s, 4), -12345., device=dev)
-                    _capi.check(_capi.lib.nfx_nerf_sigma_refine(ops._ptr(o), ops._ptr(d), ops._ptr(z), n, s, ops._ptr(blob['fp32']), ops._ptr(lst),
-                                                                ops._ptr(cnt), ops._ptr(rgbs), ops._stream()), 'nfx_nerf_sigma_refine')
-                    return rgbs
-                out[key + 'list stride 4 sigma_x3_variant %d' % v] = option('sigma_x3_variant', v, stride4)
-                out[key + 'list stride 1 sigma_x3_variant %d' % v] = option('sigma_x3_variant', v, lambda: ops.nerf_sigma_fwd_list(
-                    o, d, z, blob['fp32'], lst, cnt, torch.full((n, s), -12345., device=dev), 'fp32'))
-                out[key + 'last sample sigma_x3_variant %d' % v] = option('sigma_x3_variant', v, lambda: ops.nerf_refine_last_sample(
-                    o, d, z, torch.full((n, s, 4), -12345., device=dev), blob['fp32']))
-            # the bf16 list kernel of the occupancy march, for completeness of nfx_nerf_sigma_fwd_list
-            out[key + 'list stride 1 bf16'] = ops.nerf_sigma_fwd_list(o, d, z, blob['bf16'], lst, cnt, torch.full((n, s), -12345., device=dev), 'bf16')
+    # ------------------------------------------------------------------------------------------------------------- the kernels
+    if not pack_only:
+        dev = torch.device('cuda:0')
+        for name in pc.SETS:
+            ps = pc.point_set(name)
+            blob = {p: ops.pack_nerf_geom_weights(*common.nerf_layers(ps.net), prec=p).to(dev) for p in ('bf16', 'fp32')}
+            picked = np.random.default_rng(840).permutation(pc.N)[:333].astype(np.int32)
+            lst = torch.full((pc.N,), -1, dtype=torch.int32, device=dev)
+            lst[:333] = torch.from_numpy(picked).to(dev)
+            cnt = torch.tensor([333], dtype=torch.int32, device=dev)
+            for s in (105, 7):
+                o, d, z = (torch.from_numpy(np.array(a)).to(dev) for a in ps.layout(s))
+                n = pc.N // s
+                key = '%s/S%d/' % (name, s)
+                for v in (0, 1):
+                    out[key + 'sigma_fwd bf16 sigma_variant %d' % v] = option('sigma_variant', v, lambda: ops.nerf_sigma_fwd(o, d, z, blob['bf16'], 'bf16'))
+                    out[key + 'sigma_fwd fp32 sigma_x3_variant %d' % v] = option('sigma_x3_variant', v, lambda: ops.nerf_sigma_fwd(o, d, z, blob['fp32'], 'fp32'))
+                    for p in ('bf16', 'fp32'):
+                        nrm, sig = option('sigma_grad_rows', v, lambda: ops.nerf_sigma_grad(o, d, z, blob[p], p))
+                        out[key + 'sigma_grad %s sigma_grad_rows %d' % (p, v)] = torch.cat([nrm, sig[..., None]], -1)
+
+                    def stride4():
+                        rgbs = torch.full((n, s, 4), -12345., device=dev)
+                        _capi.check(_capi.lib.nfx_nerf_sigma_refine(ops._ptr(o), ops._ptr(d), ops._ptr(z), n, s, ops._ptr(blob['fp32']), ops._ptr(lst),
+                                                                    ops._ptr(cnt), ops._ptr(rgbs), ops._stream()), 'nfx_nerf_sigma_refine')
+                        return rgbs
+                    out[key + 'list stride 4 sigma_x3_variant %d' % v] = option('sigma_x3_variant', v, stride4)
+                    out[key + 'list stride 1 sigma_x3_variant %d' % v] = option('sigma_x3_variant', v, lambda: ops.nerf_sigma_fwd_list(
+                        o, d, z, blob['fp32'], lst, cnt, torch.full((n, s), -12345., device=dev), 'fp32'))
+                    out[key + 'last sample sigma_x3_variant %d' % v] = option('sigma_x3_variant', v, lambda: ops.nerf_refine_last_sample(
+                        o, d, z, torch.full((n, s, 4), -12345., device=dev), blob['fp32']))
+                # the bf16 list kernel of the occupancy march, for completeness of nfx_nerf_sigma_fwd_list
+                out[key + 'list stride 1 bf16'] = ops.nerf_sigma_fwd_list(o, d, z, blob['bf16'], lst, cnt, torch.full((n, s), -12345., device=dev), 'bf16')
+        torch.cuda.synchronize()
+
+
+def options(fn, **kw):
+    for k, v in kw.items():
+        if v is not None:
+            _capi.set_option(k, v)
+    try:
+        return fn()
+    finally:
+        for k, v in kw.items():
+            if v is not None:
+                _capi.unset_option(k)
+
+
+def rows_cases():
+    """The width-128 row kernels: learned BRDF in every shipped form (+ brdf_ct 8, + prec fp32), light visibility in every
+    variant and the ROWS form, the sphere preview, the BRDF backward (dense and list) and the prior on explicit rows."""
+    from tests import bwd_probes as bp, row_mlp_cases as rc, test_gpu_brdf_sphere as ts, test_gpu_row_mlp_fwd as tf
+    from tests.test_gpu_bwd_row_probes import buffers
+    to_dev = tf.dev
+    dev = torch.device('cuda:0')
+    for name in rc.SMALL + ['l512']:
+        c = rc.case(name)
+        d = tf.Dev(c, dev)
+        blob = {p: tf.pack(*rc.brdf_net(c.zd), _capi.IN_Z_RUSINK, 1, dev, z_dim=c.zd, prec=p) for p in ('bf16', 'fp32')}
+        for variant, ct in tf.brdf_forms() + [(6, 8)]:
+            out['brdf/%s variant %d brdf_ct %s' % (name, variant, ct)] = options(lambda: tf.run_brdf(d, blob['bf16']), brdf_variant=variant, brdf_ct=ct)
+        out['brdf/%s fp32' % name] = tf.run_brdf(d, blob['fp32'], prec='fp32')
+    lblob = tf.pack(*rc.lvis_net(), _capi.IN_XYZ_LDIR, 1, dev)
+    for name in rc.LVIS_CASES:
+        c = rc.case(name)
+        d = tf.Dev(c, dev)
+        for variant in tf.LVIS_VARIANTS:
+            out['lvis/%s variant %d' % (name, variant)] = options(lambda: tf.run_lvis(d, lblob), lvis_variant=variant)
+        rows = torch.from_numpy(np.random.default_rng(5).permutation(2 * c.n + 3)[:c.n].astype(np.int32)).to(dev)
+        for variant in (8, 4):
+            full = torch.full((2 * c.n + 3, c.L), -7., device=dev)
+            options(lambda: ops.lvis_fwd(d.xyz, d.lxyz, lblob, out=full, out_row=rows), lvis_variant=variant, lvis_rows=1)
+            out['lvis/%s ROWS variant %d' % (name, variant)] = full
+    for spec in ts.CASES[:2]:
+        out['sphere/%s' % (spec,)] = ts.Case(_capi, dev, *spec).run()
+    for zd in bp.BRDF_SPEC_ZDIMS:
+        nl, n = bp.BRDF_SWEEP
+        ks, bs = bp.net128(700 + zd, zd + 15, 1)
+        tblob = ops.pack_brdf_train_weights(ks, bs, zd).to(dev)
+        f = {k: to_dev(v, dev) for k, v in bp.brdf_spec_fill(n, nl, zd).items()}
+        rng = np.random.default_rng(710 + zd)
+        dspec = to_dev(rng.normal(size=(n, nl)) * (rng.uniform(size=(n, nl)) < .6), dev)      # 40 % of the rows carry no gradient
+        for rows_opt in (0, 1):
+            dz, dn = options(lambda: ops.brdf_spec_bwd(f['xyz'], f['cam'], f['normal'], f['z'], f['lxyz'], tblob, dspec), brdf_bwd_rows=rows_opt)
+            out['brdf_spec_bwd/z_dim %d brdf_bwd_rows %d' % (zd, rows_opt)] = torch.cat([dz, dn], 1)
+    ks, bs = bp.net128(bp.BRDF_ROWS_SEED, bp.BRDF_ROWS_ZDIM + 15, 1)
+    tblob = ops.pack_brdf_train_weights(ks, bs, bp.BRDF_ROWS_ZDIM).to(dev)
+    f = {k: to_dev(v, dev) for k, v in bp.brdf_rows_fill(bp.BRDF_ROWS_N).items()}
+    for reci in (False, True):
+        out['brdf_rows_fwd/reci %d' % reci] = ops.brdf_rows_fwd(f['z'], f['rusink'], tblob, reci=reci)
+        flat, dks, dbs = buffers(ks, bs, dev)
+        dout = to_dev(np.random.default_rng(720 + reci).normal(size=(1 + reci) * bp.BRDF_ROWS_N), dev)
+        out['brdf_rows_bwd/reci %d d_z' % reci] = ops.brdf_rows_bwd(f['z'], f['rusink'], tblob, dout, dks, dbs, reci=reci)
+        out['brdf_rows_bwd/reci %d dW db' % reci] = flat
     torch.cuda.synchronize()
+
+
+rows_cases() if group == 'rows' else geom_cases()
 
 out = {k: v.detach().cpu().contiguous() for k, v in out.items()}
 lib = os.environ.get('NFX_LIB_PATH', 'the tree\'s libnfx.so')

@@ -25,7 +25,7 @@ SOURCE_CONSTANTS = [
     ('lvis_v2.hip', r'kCap = NW == 8 \? 704 : kRing, kSlots = NW == 8 \? 4 : 8;'),
     ('lvis_v2.hip', r'return kLdsNet \+ NW \* kCap \* \(int\)sizeof\(ring_t\) \+ \(n_lights \* 12 \+ 15\) / 16 \* 16 \+ NW \* kSlots \* 32 \* 4;'),
     ('lvis_v2.hip', r'typedef unsigned short ring_t;'),
-    ('lvis_v2.hip', r'constexpr int kLdsNet = m128::kMainWeightBytes \+ m128::kMainBiasFloats \* 4;'),
+    ('mlp128_resident.hpp', r'constexpr int kLdsNet = m128::kMainWeightBytes \+ m128::kMainBiasFloats \* 4;'),
     ('lvis_v2.hip', r'if \(CT \* 32 - 1 \+ a\.n_lights > lv2::Queue<NW>::kCap\) return -1;'),
     ('lvis_v2.hip', r'if \(lds > 160 \* 1024\) return -1;'),
     ('lvis_v2.hip', r'if \(cnt > 0 && kfill - k_head >= kSlots - 1\) break;'),
