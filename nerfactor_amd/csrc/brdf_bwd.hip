@@ -13,6 +13,7 @@
 #include "mlp128_layout.hpp"
 #include "mlp_engine.hpp"
 #include "feat_store.hpp"
+#include "bwd_tile.hpp"
 #include "launchers.hpp"
 
 namespace nfx {
@@ -27,29 +28,8 @@ constexpr int kWeightBytes = (kFwdFrags + kBwdFrags) * 1024;
 constexpr int kBiasFloats = m128::kMainBiasFloats;
 constexpr int kBlobBytes = kWeightBytes + kBiasFloats * 4;
 
-template <int CT>
-__device__ __forceinline__ void zero_acc(f32x16 (&acc)[CT]) {
-#pragma unroll
-    for (int c = 0; c < CT; ++c)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
-}
-
-template <int KS, int NL_SELF, int NL_NEXT>
-__device__ __forceinline__ void dgrad_layer(WStream& ws, int tid, const bf16x8 (&dz)[8][1],
-                                            const bf16x8 (&hact)[8][1], bf16x8 (&dout)[8][1]) {
-    static_for<0, 4>([&](auto T) {
-        constexpr int t = decltype(T)::value;
-        f32x16 acc[1];
-        tile_init<KS, 0, (t == 3 ? NL_NEXT : NL_SELF), kNW>(
-            ws, tid, [&](f32x16(&a)[1]) { zero_acc<1>(a); }, dz, dz, acc);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float hv = (float)hact[2 * t + (r >> 3)][0][r & 7];
-            dout[2 * t + (r >> 3)][0][r & 7] = (__bf16)(hv > 0.f ? acc[0][r] : 0.f);
-        }
-    });
-}
+using bwd::dgrad_layer;   // bwd_tile.hpp
+using bwd::zero_init;
 
 constexpr double kFxScale = 1099511627776.0;   // 2^40 per unit: resolution 9e-13, range +-8e6
 __device__ __forceinline__ unsigned long long to_fx(float v) {
@@ -162,18 +142,14 @@ __global__ __launch_bounds__(kNW * 64, 1) void brdf_spec_bwd_kernel(
             constexpr int t = decltype(T)::value;
             f32x16 acc[1];
             tile_init<1, 0, (t == 3 ? 2 : 1), kNW>(
-                ws, tid, [&](f32x16(&a)[1]) { zero_acc<1>(a); }, dzo, dzo, acc);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float hv = (float)h3[2 * t + (r >> 3)][0][r & 7];
-                dz3[2 * t + (r >> 3)][0][r & 7] = (__bf16)(hv > 0.f ? acc[0][r] : 0.f);
-            }
+                ws, tid, [&](f32x16(&a)[1]) { zero_init<1>(a); }, dzo, dzo, acc);
+            bwd::relu_gate(acc[0], h3[2 * t][0], h3[2 * t + 1][0], dz3[2 * t][0], dz3[2 * t + 1][0]);
         });
         f32x16 dx[1];  // gradient w.r.t. the 32 input slots of this lane's half: reg r <-> (s = r>>3, j = r&7)
-        tile_init<8, 0, 2, kNW>(ws, tid, [&](f32x16(&a)[1]) { zero_acc<1>(a); }, dz3, dz3, dx);   // W3[128:, :] dZ3
-        dgrad_layer<8, 2, 2>(ws, tid, dz3, h2, dz2);
-        dgrad_layer<8, 2, 2>(ws, tid, dz2, h1, dz1);
-        dgrad_layer<8, 2, 2>(ws, tid, dz1, h0, dz0);
+        tile_init<8, 0, 2, kNW>(ws, tid, [&](f32x16(&a)[1]) { zero_init<1>(a); }, dz3, dz3, dx);   // W3[128:, :] dZ3
+        dgrad_layer<8, 2, 2, kNW>(ws, tid, dz3, h2, dz2);
+        dgrad_layer<8, 2, 2, kNW>(ws, tid, dz2, h1, dz1);
+        dgrad_layer<8, 2, 2, kNW>(ws, tid, dz1, h0, dz0);
         tile_init<8, 0, 1, kNW>(ws, tid, [&](f32x16(&a)[1]) {}, dz0, dz0, dx);                     // += W0 dZ0
         // ---- input slots -> d rusink, d z
         float dr[3] = {0.f, 0.f, 0.f};
@@ -342,14 +318,7 @@ __global__ __launch_bounds__(kNW * 64, 1) void brdf_rows_kernel(
         if constexpr (!BWD) {
             if (valid && h == 0) out_or_dz[row] = softplusf(logit[0][0]);   // brdf.py:65
         } else {
-            FeatStore fs;
-            {
-                unsigned long long ld2 = (unsigned long long)ld * 2, b = reinterpret_cast<unsigned long long>(wsp);
-                asm volatile("" : "+s"(ld2), "+s"(b));
-                fs.base = reinterpret_cast<char*>(b);
-                fs.ld2 = ld2;
-                fs.roff = (unsigned)(row * 4);   // pair layout: one dword per row and feature pair (feat_store.hpp)
-            }
+            const FeatStore fs = feat_store_at(wsp, ld, row);
             {   // network input, logical order [z | rusink, sin, cos bands]: half 0 / half 1 hold different features
 #pragma unroll
                 for (int q = 0; q < 6; ++q) {   // cosines sit 3 features after the sines
@@ -385,21 +354,17 @@ __global__ __launch_bounds__(kNW * 64, 1) void brdf_rows_kernel(
                 constexpr int t = decltype(T)::value;
                 f32x16 acc[1];
                 tile_init<1, 0, (t == 3 ? 2 : 1), kNW>(
-                    ws, tid, [&](f32x16(&a)[1]) { zero_acc<1>(a); }, dzo, dzo, acc);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float hv = (float)h3[2 * t + (r >> 3)][0][r & 7];
-                    dz3[2 * t + (r >> 3)][0][r & 7] = (__bf16)(hv > 0.f ? acc[0][r] : 0.f);
-                }
+                    ws, tid, [&](f32x16(&a)[1]) { zero_init<1>(a); }, dzo, dzo, acc);
+                bwd::relu_gate(acc[0], h3[2 * t][0], h3[2 * t + 1][0], dz3[2 * t][0], dz3[2 * t + 1][0]);
             });
             store_hidden<8>(fs, kOffDZ + 384, h, dz3);
             f32x16 dx[1];  // gradient w.r.t. the 32 input slots of this lane's half
-            tile_init<8, 0, 2, kNW>(ws, tid, [&](f32x16(&a)[1]) { zero_acc<1>(a); }, dz3, dz3, dx);   // W3[128:, :] dZ3
-            dgrad_layer<8, 2, 2>(ws, tid, dz3, h2, dz2);
+            tile_init<8, 0, 2, kNW>(ws, tid, [&](f32x16(&a)[1]) { zero_init<1>(a); }, dz3, dz3, dx);   // W3[128:, :] dZ3
+            dgrad_layer<8, 2, 2, kNW>(ws, tid, dz3, h2, dz2);
             store_hidden<8>(fs, kOffDZ + 256, h, dz2);
-            dgrad_layer<8, 2, 2>(ws, tid, dz2, h1, dz1);
+            dgrad_layer<8, 2, 2, kNW>(ws, tid, dz2, h1, dz1);
             store_hidden<8>(fs, kOffDZ + 128, h, dz1);
-            dgrad_layer<8, 2, 2>(ws, tid, dz1, h0, dz0);
+            dgrad_layer<8, 2, 2, kNW>(ws, tid, dz1, h0, dz0);
             store_hidden<8>(fs, kOffDZ + 0, h, dz0);
             tile_init<8, 0, 1, kNW>(ws, tid, [&](f32x16(&a)[1]) {}, dz0, dz0, dx);                     // += W0 dZ0
             if (valid) {   // d z: slot (k-step 0, elem 7) of half 1 holds z_0, k-step 1 elem j of half hh holds z_{1+2j+hh}

@@ -1,5 +1,5 @@
 // feat_store.hpp — bf16 stores of register-resident activations / gradients for the weight-gradient GEMMs (train.hip),
-// shared by the fused backward kernels (mlp128_bwd.hip, nerf_bwd.hip, brdf_bwd.hip).
+// shared by the fused backward kernels (mlp128_bwd.hip, nerf_bwd.hip, brdf_bwd.hip; bwd_tile.hpp builds on it).
 //
 // Layout (round 3): FEATURE-PAIR-major, [pair = feature >> 1][row][feature & 1] bf16 — a dword holds two adjacent
 // features of one row.  That is what a B-operand register already is (v_cvt_pk_bf16_f32 packs features f, f + 1 of the
@@ -26,6 +26,16 @@ struct FeatStore {
     unsigned long long ld2;
     unsigned roff;  // row * 4: the row's dword inside a pair row (callers add 4 * ld2 per 4 features for lane half 1)
 };
+// the FeatStore of workspace row `row` (`ld` rows per feature), formed once per tile
+__device__ __forceinline__ FeatStore feat_store_at(__bf16* wsp, long long ld, long long row) {
+    unsigned long long ld2 = (unsigned long long)ld * 2, b = reinterpret_cast<unsigned long long>(wsp);
+    asm volatile("" : "+s"(ld2), "+s"(b));
+    FeatStore fs;
+    fs.base = reinterpret_cast<char*>(b);
+    fs.ld2 = ld2;
+    fs.roff = (unsigned)(row * 4);   // pair layout: one dword per row and feature pair
+    return fs;
+}
 // Re-materialises the uniform base / stride behind an opaque asm so the per-feature base addresses of the NEXT
 // group of stores are computed next to those stores (not hoisted to the top of the tile and spilled).
 __device__ __forceinline__ FeatStore relaunder(const FeatStore& fs) {

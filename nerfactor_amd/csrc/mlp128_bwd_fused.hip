@@ -7,7 +7,7 @@
 // (profiles/HISTORY.md section 3b).  Here nothing but the weight gradients leaves the CU:
 //
 //   * one workgroup = 4 waves x 32 rows, persistent over its 128-row tiles; per tile it re-computes the forward and
-//     runs the dgrad chain exactly like mlp128_bwd_ring_kernel (same MFMA order, same operand registers);
+//     runs the dgrad chain with the MFMA order and operand registers of mlp128_bwd_ring_kernel (dZ_out: bwd_tile.hpp);
 //   * when dZ_l of a tile exists, each wave writes its 32 rows of dZ_l and of the layer's input H_{l-1} ROW-MAJOR into
 //     two LDS buffers ([128 rows][128 slots] bf16, one ds_write_b128 per B-operand register: a lane holds 8 slots of
 //     its row), and after one barrier reads them back with the TRANSPOSING LDS load of gfx950
@@ -28,8 +28,8 @@
 //     2.3 KB of HBM traffic per row removed.  (The first split — layer 3, out, layer 0 | layers 2, 1, both running the
 //     whole chain, bias by all-ones MFMA blocks — measured 571 + 564 us per 1 048 576 rows: profiles/r04/call_c.)
 //   * ALL weights (forward + dgrad, 248-304 KiB per tile from L2) stream through the 5-slot LDS-DMA ring of
-//     mlp128_bwd.hip, extended by the 14 dgrad sub-chunks: with no store in the tile loop the counted vmcnt waits see
-//     DMA pieces (and the tile's few input loads, which only make a wait conservative).
+//     mlp128_bwd_ring.hpp, the forward table extended by the 14 dgrad sub-chunks: with no store in the tile loop the
+//     counted vmcnt waits see DMA pieces (and the tile's few input loads, which only make a wait conservative).
 // LDS: ring 40 KiB | biases | X rows | H rows | dZ rows = 141 568 bytes.  The three row buffers are [128 rows][64 dwords]
 // with NO padding and an XOR swizzle of the dword index by the row (swz_bytes below, round 5).  Round 4 padded the rows to
 // 72 dwords: under the LDS's banking rules (MI355X_MICROARCH.md: ds_write_b128 = 8 lanes x 4 dwords over 32 banks,
@@ -42,6 +42,8 @@
 #include "mlp_engine.hpp"
 #include "lds_dma.hpp"
 #include "mlp128_train_layout.hpp"
+#include "bwd_tile.hpp"
+#include "mlp128_bwd_ring.hpp"
 #include "tr16.hpp"
 #include "launchers.hpp"
 
@@ -50,8 +52,12 @@ namespace bwd {
 namespace fused {
 
 constexpr int kNW = 4, kRows = kNW * 32;
-constexpr int kR = 5, kD = kR - 1, kSlot = 8192;
-constexpr int kFwdSub = 21;   // sub-chunks per tile: forward 0-20, dgrad through `out` 21-22, W3 23-26, W2 27-30, W1 31-34
+static_assert(kNW == ring::kNW, "waves per ring");
+using ring::kR;       // the weight ring: mlp128_bwd_ring.hpp
+using ring::kD;
+using ring::kSlot;
+using ring::Ctx;
+// sub-chunks per tile: forward 0-20, dgrad through `out` 21-22, W3 23-26, W2 27-30, W1 31-34
 // PART 0 (layers 3 and out) stops behind dZ3: 23 sub-chunks per tile; PART 1 (layers 2, 1, 0) runs the whole chain: 35
 constexpr int sub_n(int part) { return part == 0 ? 23 : 35; }
 constexpr int kHPitch = 128 * 2;          // bytes per row of the X / H / dZ buffers (64 dwords, swizzled)
@@ -82,30 +88,11 @@ __device__ __forceinline__ bf16x8 tr_frag2(const char* lo_p, const char* hi_p) {
     return __builtin_bit_cast(bf16x8, v);
 }
 
+// pieces that may still be in flight at the barrier that ends sub-chunk k: those of k + 3 ... k + kD.  k + 1 AND k + 2 have
+// landed for every wave behind it (round 5: the first fragments of sub-chunk k + 2 are read while k + 1 multiplies — see
+// sub_mma; until then the barrier guaranteed k + 1 only and every sub-chunk began with "read, wait ~130 cycles, MFMA")
 template <int KSX, int NS>
-struct Sub {
-    using G = Geo<KSX>;
-    static constexpr int frags(int k) {
-        return k < 4 ? G::kP0 : k < 12 ? 8 : k < 20 ? ((k - 12) % 2 == 0 ? 8 : G::kP3 - 8) : 8;
-    }
-    static constexpr int off(int k) {   // first fragment in the train blob
-        return k < 4 ? k * G::kP0 : k < 8 ? 4 * G::kP0 + (k - 4) * 8 : k < 12 ? 4 * G::kP0 + 32 + (k - 8) * 8
-             : k < 20 ? 4 * G::kP0 + 64 + ((k - 12) / 2) * G::kP3 + ((k - 12) % 2) * 8
-             : k == 20 ? 4 * G::kP0 + 64 + 4 * G::kP3
-             : G::kFwdFrags + (k - kFwdSub) * 8;   // the 112 dgrad fragments are contiguous: 14 sub-chunks of 8
-    }
-    static constexpr int pieces(int k) { return frags(k) / kNW; }   // 1-KiB pieces per wave: 1 | 2
-    // pieces that may still be in flight at the barrier that ends sub-chunk k: those of k + 3 ... k + kD.  k + 1 AND k + 2 have
-    // landed for every wave behind it (round 5: the first fragments of sub-chunk k + 2 are read while k + 1 multiplies — see
-    // sub_mma; until then the barrier guaranteed k + 1 only and every sub-chunk began with "read, wait ~130 cycles, MFMA")
-    static constexpr int allow(int k) {
-        int n = 0;
-        for (int j = 3; j <= kD; ++j) n += pieces((k + j) % NS);
-        return n;
-    }
-};
-static_assert(Sub<6, 35>::off(kFwdSub) == Geo<6>::kFwdFrags && Sub<6, 35>::off(34) + 8 == Geo<6>::kFwdFrags + Geo<6>::kBwdFrags, "blob");
-static_assert(Sub<4, 35>::off(kFwdSub) == Geo<4>::kFwdFrags && Sub<4, 35>::off(34) + 8 == Geo<4>::kFwdFrags + Geo<4>::kBwdFrags, "blob");
+using Sub = ring::Sub<KSX, NS, 3>;
 
 template <int KSX>
 struct Lds {
@@ -131,33 +118,6 @@ struct Blocks {
     static constexpr int NACC = PART == 0 ? 5 + NX : 8 + NX, kBias = NACC, N = NACC + 1;
 };
 
-struct Ctx {
-    char* smem;
-    unsigned smem_lds;
-    const char* blob;
-    int lane, wave;   // wave: wave-uniform
-    int cur;          // ring slot of the sub-chunk being consumed (wave-uniform)
-};
-template <int KSX, int NS, int K>
-__device__ __forceinline__ void begin(const Ctx& cx) {
-    constexpr int F = (K + kD) % NS, n = Sub<KSX, NS>::pieces(F);
-    unsigned long long base = reinterpret_cast<unsigned long long>(cx.blob);
-    unsigned lds = cx.smem_lds;
-    asm volatile("" : "+s"(base), "+s"(lds));   // per sub-chunk: keeps the addresses out of the loop preheader
-    int slot = cx.cur + kD;
-    slot = slot >= kR ? slot - kR : slot;
-    const int piece0 = cx.wave * n;
-    lds_dma_pieces<n>((unsigned)cx.lane * 16u, reinterpret_cast<const char*>(base) + (size_t)Sub<KSX, NS>::off(F) * 1024 + piece0 * 1024,
-                      lds + (unsigned)slot * kSlot + (unsigned)piece0 * 1024u);
-}
-// LGKM: the LDS reads that may still be in flight across the barrier — the NEXT sub-chunk's carry fragments, issued last.
-// Everything older (this sub-chunk's own fragment reads: the compiler is free to sink their MFMAs below the barrier) has
-// returned before the wave arrives, so no wave's DMA into this slot (begin<K + 1>) can overtake a read of it.
-template <int KSX, int NS, int K, int LGKM>
-__device__ __forceinline__ void end(Ctx& cx) {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(%1)\n\ts_barrier" ::"n"(Sub<KSX, NS>::allow(K)), "n"(LGKM) : "memory");
-    cx.cur = cx.cur + 1 == kR ? 0 : cx.cur + 1;
-}
 // Fragment reads and MFMAs of one sub-chunk, software-pipelined ACROSS sub-chunks (round 5).  With one wave per SIMD nothing
 // hides the ~130 cycles between a ds_read_b128 and its first use but the wave's own MFMAs, and the ring's barrier sits in
 // front of every sub-chunk: "barrier, 8 reads, wait, MFMAs" exposed that latency 35 times per 128-row tile (the ISA of r04 /
@@ -196,7 +156,7 @@ __device__ __forceinline__ void sub_mma(Ctx& cx, Carry& c, const bf16x8 (&b)[KSA
     }
 #pragma unroll
     for (int s = 0; s < R; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rest[s], b[H + s][0], acc, 0, 0, 0);
-    end<KSX, NS, K, NEXT>(cx);
+    ring::end<Sub<KSX, NS>, K, NEXT>(cx);      // in flight across the barrier: the NEXT carry fragments, issued last
 }
 // ---- packed 16-bit epilogues (the kernels are VALU-bound beside their MFMAs: r04 call C counted ~3300 VALU instructions
 // per 128-row tile and wave against 340 matrix instructions; the scalar forms — v_med3 + v_cvt per value, bf16 -> f32 +
@@ -257,7 +217,7 @@ __device__ __forceinline__ void layer(Ctx& cx, Carry& c, const float* bias, cons
     };
     static_for<0, 4>([&](auto T) {
         constexpr int t = decltype(T)::value;
-        begin<KSX, NS, K0 + t>(cx);
+        ring::begin<Sub<KSX, NS>, K0 + t>(cx);
         f32x16 acc[1];
         bias_init<1>(bias + 32 * t, cx.lane >> 5, acc);      // (broadcast reads: in flight under the epilogue as well)
         sub_mma<KSX, NS, K0 + t, KS, (t > 0 || HAVE), (t < 3 ? (KS < kCarry ? KS : kCarry) : NEXT)>(cx, c, b, acc[0], [&]() {
@@ -305,7 +265,7 @@ __device__ __forceinline__ void dgrad(Ctx& cx, Carry& c, const bf16x8 (&dz)[8][1
     f32x16 prev;
     static_for<0, 4>([&](auto T) {
         constexpr int t = decltype(T)::value;
-        begin<KSX, NS, K0 + t>(cx);
+        ring::begin<Sub<KSX, NS>, K0 + t>(cx);
         f32x16 acc[1];
         zero_acc(acc[0]);
         sub_mma<KSX, NS, K0 + t, 8, (t > 0 || HAVE), (t < 3 ? kCarry : 0)>(cx, c, dz, acc[0], [&]() {   // (a weight-gradient section follows tile 3)
@@ -412,7 +372,7 @@ __global__ __launch_bounds__(kNW * 64, 1) void mlp128_bwd_fused_kernel(
         const float* bsrc = reinterpret_cast<const float*>(blob + G::kWeightBytes);
         for (int i = tid; i < G::kBiasFloats; i += kNW * 64) bias_lds[i] = bsrc[i];
 #pragma unroll
-        for (int k = 0; k < kD; ++k) {   // sub-chunks 0 .. kD-1 of the first tile -> slots 0 .. kD-1
+        for (int k = 0; k < kD; ++k) {   // sub-chunks 0 .. kD-1 of the first tile -> slots 0 .. kD-1 (ring::prologue, written out)
             const u32x4* src = reinterpret_cast<const u32x4*>(blob + (size_t)S::off(k) * 1024);
             u32x4* dst = reinterpret_cast<u32x4*>(smem + k * kSlot);
             for (int i = tid; i < S::frags(k) * 64; i += kNW * 64) dst[i] = src[i];
@@ -485,7 +445,7 @@ __global__ __launch_bounds__(kNW * 64, 1) void mlp128_bwd_fused_kernel(
 #pragma unroll
         for (int r = 0; r < 4; ++r) dv[r] = ndv[r];
         fetch(tile + gridDim.x < n_tiles ? tile + gridDim.x : tile);
-        bf16x8 xin[KSX][1];
+        bf16x8 xin[KSX][1];   // (bwd_tile.hpp:row_operand, written out: the function moves this kernel's instructions)
         {
             bf16x8 pe[4][1];
             posenc<10, 1>(x, h, 0, pe);
@@ -522,20 +482,20 @@ __global__ __launch_bounds__(kNW * 64, 1) void mlp128_bwd_fused_kernel(
             f32x16 prev3;
             static_for<0, 4>([&](auto T) {   // layer 3: [h2 ; input], two sub-chunks per tile
                 constexpr int t = decltype(T)::value;
-                begin<KSX, NS, 12 + 2 * t>(cx);
+                ring::begin<Sub<KSX, NS>, 12 + 2 * t>(cx);
                 f32x16 a3[1];
                 bias_init<1>(bias_lds + 384 + 32 * t, h, a3);
                 sub_mma<KSX, NS, 12 + 2 * t, 8, true, kXc>(cx, cr, h2, a3[0], [&]() {
                     if constexpr (t > 0) relu_tile<kBits>(prev3, h3[2 * t - 2][0], h3[2 * t - 1][0], m3[t - 1]);   // (under the reads)
                 });
-                begin<KSX, NS, 13 + 2 * t>(cx);
+                ring::begin<Sub<KSX, NS>, 13 + 2 * t>(cx);
                 sub_mma<KSX, NS, 13 + 2 * t, KSX, true, kCarry>(cx, cr, xin, a3[0], []() {});   // next: tile t + 1's h2 part, or `out`
                 prev3 = a3[0];
             });
             relu_tile<kBits>(prev3, h3[6][0], h3[7][0], m3[3]);
         }
         f32x16 logit[1];
-        begin<KSX, NS, 20>(cx);
+        ring::begin<Sub<KSX, NS>, 20>(cx);
         bias_init<1>(bias_lds + 512, h, logit);
         // (PART 0: the out layer's weight-gradient section sits between sub-chunks 20 and 21 — no carry across it)
         sub_mma<KSX, NS, 20, 8, true, (PART == 1 ? 1 : 0)>(cx, cr, h3, logit[0], []() {});
@@ -543,8 +503,7 @@ __global__ __launch_bounds__(kNW * 64, 1) void mlp128_bwd_fused_kernel(
         bf16x8 dzo[1][1];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float g = dv[r] * post_scale * act_grad(logit[0][r], out_act);
-            dzo[0][0][r] = (__bf16)((valid && 4 * h + r < out_dim) ? g : 0.f);
+            dzo[0][0][r] = dz_out(dv[r], logit[0][r], post_scale, out_act, valid && 4 * h + r < out_dim);
             dzo[0][0][4 + r] = (__bf16)0.f;
         }
         if constexpr (PART == 0) {   // out layer: dWo[i, f] = sum h3[row, i] dZo[row, f]; wave w takes h3 slots [32 w, +32)
@@ -558,7 +517,7 @@ __global__ __launch_bounds__(kNW * 64, 1) void mlp128_bwd_fused_kernel(
         {   // through the out layer: one k-step (16 padded output slots); tiles 0, 1 in sub-chunk 21, tiles 2, 3 in 22
             static_for<0, 2>([&](auto U) {      // fragments 0 and 4 of the sub-chunk: 0 rides in the carry
                 constexpr int u = decltype(U)::value;
-                begin<KSX, NS, 21 + u>(cx);
+                ring::begin<Sub<KSX, NS>, 21 + u>(cx);
                 f32x16 a0[1], a1[1];
                 zero_acc(a0[0]);
                 zero_acc(a1[0]);
@@ -573,7 +532,7 @@ __global__ __launch_bounds__(kNW * 64, 1) void mlp128_bwd_fused_kernel(
                     __builtin_amdgcn_sched_barrier(kSchedAluOnly);
                 }
                 a1[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f4[0], dzo[0][0], a1[0], 0, 0, 0);
-                end<KSX, NS, 21 + u, (u == 0 ? 1 : PART == 1 ? kCarry : 0)>(cx);
+                ring::end<Sub<KSX, NS>, 21 + u, (u == 0 ? 1 : PART == 1 ? kCarry : 0)>(cx);
                 relu_mask<kBits ? 1 : 0>(a0[0], h3, m3, nullptr, 0, 2 * u, dz3[4 * u][0], dz3[4 * u + 1][0]);
                 relu_mask<kBits ? 1 : 0>(a1[0], h3, m3, nullptr, 0, 2 * u + 1, dz3[4 * u + 2][0], dz3[4 * u + 3][0]);
             });

@@ -22,6 +22,34 @@ constexpr int kNerfNW = 4;  // one wave per SIMD (launch_bounds(256, 1): up to 5
 constexpr int kNerfRows = kNerfNW * 32;
 constexpr int kNerfBwdLds = 2 * kSlotBytes + nerf::kBiasFloats * 4;
 
+// ---- the chunk epilogues that the register-staged kernel and the ring kernel share
+// forward epilogue of tile T: the activation goes to the next B operand (lo / hi), to the feature-major workspace (rows
+// feat0 ..) and, for ReLU layers, to the mask words m[T >> 1].  kEpiStores dword stores.
+template <bool RELU, int T, int NM>
+__device__ __forceinline__ void fwd_epilogue(const f32x16 (&acc)[1], bf16x8 (&lo)[1], bf16x8 (&hi)[1], const FeatStore& fs,
+                                             int feat0, int h, unsigned (&m)[NM]) {
+    if constexpr (RELU) {
+        const unsigned bits = relu_bits16(acc[0]);
+        if constexpr (T & 1) m[T >> 1] |= bits << 16;
+        else m[T >> 1] = bits;
+    }
+    acc_to_b<RELU, 1>(acc, lo, hi);
+    store_tile(fs, feat0, h, lo[0], hi[0]);
+    __builtin_amdgcn_sched_barrier(0);
+}
+// dgrad epilogue of tile t: masked by the bits of `m` (MASK), to the next dZ operand and the workspace.  kEpiStores dword stores.
+template <bool MASK, int NM, int NTA>
+__device__ __forceinline__ void dgrad_epilogue(const f32x16 (&acc)[1], const unsigned (&m)[NM], int t, bf16x8 (&dout)[NTA][1],
+                                               const FeatStore& fs, int feat0, int h) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const bool on = MASK ? mask_bit(m, t, r) : true;
+        dout[2 * t + (r >> 3)][0][r & 7] = (__bf16)(on ? acc[0][r] : 0.f);
+    }
+    store_tile(fs, feat0, h, dout[2 * t][0], dout[2 * t + 1][0]);
+    __builtin_amdgcn_sched_barrier(0);
+}
+
 // Forward layer of the re-computation: NT tiles; each tile's activation goes to the next B operand, to the
 // feature-major workspace (rows feat0 + 32 t ..) and, for ReLU layers, to the mask words m[t>>1].
 template <int KS1, int KS2, int NT, int NL_SELF, int NL_NEXT, bool RELU, int KS1A, int KS2A, int NTA>
@@ -33,14 +61,7 @@ __device__ __forceinline__ void fwd_layer(WStream& ws, int tid, const float* bia
         constexpr int t = decltype(T)::value;
         f32x16 acc[1];
         tile_raw<KS1, KS2, (t == NT - 1 ? NL_NEXT : NL_SELF), kNerfNW>(ws, tid, bias + 32 * t, b1, b2, acc);
-        if constexpr (RELU) {
-            const unsigned bits = relu_bits16(acc[0]);
-            if constexpr (t & 1) m[t >> 1] |= bits << 16;
-            else m[t >> 1] = bits;
-        }
-        acc_to_b<RELU, 1>(acc, bout[2 * t], bout[2 * t + 1]);
-        store_tile(fs, feat0 + 32 * t, h, bout[2 * t][0], bout[2 * t + 1][0]);
-        __builtin_amdgcn_sched_barrier(0);
+        fwd_epilogue<RELU, t>(acc, bout[2 * t], bout[2 * t + 1], fs, feat0 + 32 * t, h, m);
     });
 }
 
@@ -56,13 +77,7 @@ __device__ __forceinline__ void dgrad_layer(WStream& ws, int tid, const bf16x8 (
         f32x16 acc[1];
         tile_init<KS1, KS2, (t == NT - 1 ? NL_NEXT : NL_SELF), kNerfNW>(
             ws, tid, [&](f32x16(&a)[1]) { zero_init<1>(a); }, dz, b2, acc);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const bool on = MASK ? mask_bit(m, t, r) : true;
-            dout[2 * t + (r >> 3)][0][r & 7] = (__bf16)(on ? acc[0][r] : 0.f);
-        }
-        store_tile(fs, feat0 + 32 * t, h, dout[2 * t][0], dout[2 * t + 1][0]);
-        __builtin_amdgcn_sched_barrier(0);
+        dgrad_epilogue<MASK>(acc, m, t, dout, fs, feat0 + 32 * t, h);
     });
 }
 
@@ -88,14 +103,7 @@ __global__ __launch_bounds__(kNerfNW * 64, 1) void nerf_bwd_kernel(
     const long long n_tiles = (n_pts + kNerfRows - 1) / kNerfRows;
     for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const long long row = tile * kNerfRows + wave * 32 + p;  // < ld (ld is a multiple of kNerfRows)
-        FeatStore fs;
-        {
-            unsigned long long ld2 = (unsigned long long)ld * 2, b = reinterpret_cast<unsigned long long>(wsp);
-            asm volatile("" : "+s"(ld2), "+s"(b));
-            fs.base = reinterpret_cast<char*>(b);
-            fs.ld2 = ld2;
-            fs.roff = (unsigned)(row * 4);   // pair layout: one dword per row and feature pair (feat_store.hpp)
-        }
+        const FeatStore fs = feat_store_at(wsp, ld, row);
         const bool valid = row < n_pts;
         const long long mm = valid ? row : n_pts - 1;
         bf16x8 pe[4][1], pv[2][1];
@@ -286,14 +294,7 @@ __device__ __forceinline__ void fwd_layer(const Ctx& cx, int bias_off, const bf1
         f32x16 acc[1];
         bias_acc(cx, bias_off + 32 * t, acc[0]);
         chunk<NW, I0 + t, KS1, KS2>(cx, b1, b2, acc);
-        if constexpr (RELU) {
-            const unsigned bits = relu_bits16(acc[0]);
-            if constexpr (t & 1) m[t >> 1] |= bits << 16;
-            else m[t >> 1] = bits;
-        }
-        acc_to_b<RELU, 1>(acc, bout[2 * t], bout[2 * t + 1]);
-        store_tile(fs, feat0 + 32 * t, h, bout[2 * t][0], bout[2 * t + 1][0]);   // kEpiStores dword stores
-        __builtin_amdgcn_sched_barrier(0);
+        fwd_epilogue<RELU, t>(acc, bout[2 * t], bout[2 * t + 1], fs, feat0 + 32 * t, h, m);
     });
 }
 template <int NW, int I0, int KS1, int KS2, int NT, bool MASK, int KS1A, int KS2A, int NTA>
@@ -306,13 +307,7 @@ __device__ __forceinline__ void dgrad_layer(const Ctx& cx, const bf16x8 (&dz)[KS
         f32x16 acc[1];
         zero_init<1>(acc);
         chunk<NW, I0 + t, KS1, KS2>(cx, dz, b2, acc);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const bool on = MASK ? mask_bit(m, t, r) : true;
-            dout[2 * t + (r >> 3)][0][r & 7] = (__bf16)(on ? acc[0][r] : 0.f);
-        }
-        store_tile(fs, feat0 + 32 * t, h, dout[2 * t][0], dout[2 * t + 1][0]);   // kEpiStores dword stores
-        __builtin_amdgcn_sched_barrier(0);
+        dgrad_epilogue<MASK>(acc, m, t, dout, fs, feat0 + 32 * t, h);
     });
 }
 }  // namespace nring
@@ -345,14 +340,7 @@ __global__ __launch_bounds__(NW * 64, 1) void nerf_bwd_ring_kernel(
     const long long n_tiles = (n_act + kRows - 1) / kRows;
     for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const long long row = tile * kRows + wave * 32 + p;  // < ld (ld is a multiple of 256)
-        FeatStore fs;
-        {
-            unsigned long long ld2 = (unsigned long long)ld * 2, b = reinterpret_cast<unsigned long long>(wsp);
-            asm volatile("" : "+s"(ld2), "+s"(b));
-            fs.base = reinterpret_cast<char*>(b);
-            fs.ld2 = ld2;
-            fs.roff = (unsigned)(row * 4);
-        }
+        const FeatStore fs = feat_store_at(wsp, ld, row);
         const bool valid = row < n_act;
         long long mm = valid ? row : n_pts - 1;
         if constexpr (LIST) {
@@ -481,8 +469,6 @@ extern "C" int nfx_launch_nerf_bwd(const float* rayo, const float* rayd, const f
                                    hipStream_t st, void* list_ws) {
     using namespace nfx;
     if (n_pts <= 0) return 0;
-    const long long tiles = (n_pts + bwd::kNerfRows - 1) / bwd::kNerfRows;
-    const int grid = (int)(tiles < max_blocks ? tiles : max_blocks);
     // r03 default: weights through the LDS-DMA ring; NFX_NERF_BWD=0 keeps the register-staged kernel (identity reference)
     const bool use_ring = nfx_option_int("nerf_bwd", 1) != 0;            // (per call, like every knob: INTEGRATION.md)
     const int ring_nw = nfx_option_int("nerf_bwd_nw", 8) == 4 ? 4 : 8;
@@ -499,11 +485,11 @@ extern "C" int nfx_launch_nerf_bwd(const float* rayo, const float* rayd, const f
                             : (list ? bwd::nerf_bwd_ring_kernel<4, true> : bwd::nerf_bwd_ring_kernel<4, false>);
     const int nw = use_ring ? ring_nw : bwd::kNerfNW;
     const int lds = !use_ring ? bwd::kNerfBwdLds : ring_nw == 8 ? bwd::nring::Cfg<8>::kLds : bwd::nring::Cfg<4>::kLds;
-    const long long tiles_nw = (n_pts + nw * 32 - 1) / (nw * 32);
-    const int grid_nw = (int)(tiles_nw < max_blocks ? tiles_nw : max_blocks);
+    const long long tiles = (n_pts + nw * 32 - 1) / (nw * 32);
+    const int grid = (int)(tiles < max_blocks ? tiles : max_blocks);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k, dim3(grid_nw), dim3(nw * 64), lds, st, rayo, rayd, z, n_pts, n_samples,
+    hipLaunchKernelGGL(k, dim3(grid), dim3(nw * 64), lds, st, rayo, rayd, z, n_pts, n_samples,
                        (const char*)blob, (const float4*)d_rgbs, (__bf16*)wsp, ld, (const int*)list, (const int*)count);
     return (int)hipGetLastError();
 }

@@ -2,13 +2,16 @@
 that must not change a single bit.  One process per library:
     NFX_LIB_PATH=old.so python scripts/geom_identity.py save;  python scripts/geom_identity.py check
     ... save --pack-only / check --pack-only: the packers alone (no GPU)
-    ... save --group rows / check --group rows: the second group of cases
+    ... save --group rows / check --group rows, save --group bwd / check --group bwd: the other groups of cases
 --group geom (the default): the density / density-gradient kernels (nerf_geom.hip, nerf_geom_x3.hip, nerf_sigma_x3_pipe.hip)
   and the bytes of the fp32-class packers, on the 840-point sets of tests/nerf_point_cases.py ('glorot', 'fitted'), as
   [8, 105] and [120, 7].
 --group rows: the width-128 row kernels behind brdf_row.hpp and mlp128_resident.hpp (lvis_v2.hip, mlp128.hip, mlp128_x3.hip,
   brdf_sphere.hip, brdf_bwd.hip) on the seeded cases of tests/row_mlp_cases.py, tests/test_gpu_brdf_sphere.py and
-  tests/bwd_probes.py."""
+  tests/bwd_probes.py.
+--group bwd: the training backward kernels behind bwd_tile.hpp and mlp128_bwd_ring.hpp (mlp128_bwd.hip, mlp128_bwd_fused.hip,
+  nerf_bwd.hip) on the launch shapes of tests/bwd_probes.py, with dense seeded upstream gradients of which about 40 % of the
+  rows are exact zeros, under every path and option that selects another kernel."""
 import hashlib
 import os
 import sys
@@ -28,8 +31,8 @@ from tests import common, nerf_point_cases as pc  # noqa: E402
 mode = sys.argv[1]
 pack_only = '--pack-only' in sys.argv
 group = sys.argv[sys.argv.index('--group') + 1] if '--group' in sys.argv else 'geom'
-assert group in ('geom', 'rows') and not (pack_only and group == 'rows')
-path = os.path.join(ROOT, 'build', 'geom_identity_pack.pt' if pack_only else 'geom_identity.pt' if group == 'geom' else 'geom_identity_rows.pt')     # build/ is not tracked
+assert group in ('geom', 'rows', 'bwd') and not (pack_only and group != 'geom')
+path = os.path.join(ROOT, 'build', 'geom_identity_pack.pt' if pack_only else 'geom_identity.pt' if group == 'geom' else 'geom_identity_%s.pt' % group)     # build/ is not tracked
 out = {}
 
 
@@ -152,7 +155,55 @@ def rows_cases():
     torch.cuda.synchronize()
 
 
-rows_cases() if group == 'rows' else geom_cases()
+def bwd_cases():
+    """The gradient buffer (every dW and db, flat) of the width-128 backward (IN_XYZ: 260 rows, one net per output activation;
+    IN_XYZ_LDIR: 32 lights x 9 points; the three-head launch: 260 rows) under fused / fused1 / fused3 / gemm0 / gemm1, the gemm
+    paths with the register-staged and the ring kernel, and of the NeRF backward (3 x 87 and 9 x 128 points) with the
+    register-staged kernel and the ring kernel at 4 and 8 waves, with and without the row list, behind both GEMM forms."""
+    from tests import bwd_probes as bp
+    from tests.test_gpu_bwd_row_probes import Ldir, Nerf, Xyz, dev as to_dev
+    dev = torch.device('cuda:0')
+
+    def sparse_rows(seed, rows, width):      # dense values; about 40 % of the rows are exact zeros
+        rng = np.random.default_rng(seed)
+        return to_dev(rng.normal(size=(rows, width)) * (rng.uniform(size=(rows, 1)) < .6), dev)
+
+    paths = [('fused', dict(wgrad_fused=1)), ('fused1', dict(wgrad_fused=1, m128_blocks=1)), ('fused3', dict(wgrad_fused=1, m128_blocks=3))]
+    paths += [('gemm%d m128_bwd %d' % (lds, ring), dict(wgrad_fused=0, wgrad_lds=lds, m128_bwd=ring)) for lds in (0, 1) for ring in (0, 1)]
+    n = bp.N_SWEEP
+    x = to_dev(bp.xyz_fill(n)['xyz'], dev)
+    xyz = {name: Xyz(_capi, dev, name) for name in bp.HEAD_NETS}
+    douts = {name: sparse_rows(800 + i, n, t.p.out_dim) for i, (name, t) in enumerate(xyz.items())}
+    ld = Ldir(_capi, dev)
+    nl, npt = bp.LDIR_SWEEP
+    lf = {k: to_dev(v, dev) for k, v in bp.ldir_fill(npt, nl).items()}
+    ldout = sparse_rows(810, npt * nl, 1).reshape(npt, nl).contiguous()
+    for pname, kw in paths:
+        for name in bp.SWEEP_NETS:
+            out['mlp128_bwd xyz/%s %s' % (name, pname)] = options(lambda: xyz[name].run(x, douts[name]).clone(), **kw)
+        out['mlp128_bwd xyz+ldir/%s' % pname] = options(lambda: ld.run(lf['xyz'], lf['xyz_dir'], lf['lxyz'], ldout).clone(), **kw)
+
+        def heads():
+            for t in xyz.values():
+                t.flat.zero_()
+            ops.mlp128_bwd_heads(_capi.IN_XYZ, x, [(douts[name], t.blob, t.dks, t.dbs, t.p.act, t.p.post) for name, t in xyz.items()],
+                                 xyz_scale=bp.XYZ_SCALE)
+            return torch.cat([t.flat for t in xyz.values()])
+        out['mlp128_bwd_heads/%s' % pname] = options(heads, **kw)
+    nerf = Nerf(dev)
+    forms = [('nerf_bwd 0', dict(nerf_bwd=0))]
+    forms += [('nerf_bwd 1 nerf_bwd_nw %d nerf_bwd_rows %d' % (nw, rows), dict(nerf_bwd=1, nerf_bwd_nw=nw, nerf_bwd_rows=rows)) for nw in (4, 8) for rows in (0, 1)]
+    for rays, s in (bp.NERF_SWEEP, bp.NERF_PAIR):
+        f, _ = nerf.batch(rays, s)
+        d = sparse_rows(820 + s, rays * s, 4).reshape(rays, s, 4).contiguous()
+        for fname, kw in forms:
+            for lds in (0, 1):
+                out['nerf_mlp_bwd/%dx%d %s wgrad_lds %d' % (rays, s, fname, lds)] = options(
+                    lambda: nerf.run(f['rayo'], f['rayd'], f['z'], d).clone(), wgrad_lds=lds, **kw)
+    torch.cuda.synchronize()
+
+
+{'geom': geom_cases, 'rows': rows_cases, 'bwd': bwd_cases}[group]()
 
 out = {k: v.detach().cpu().contiguous() for k, v in out.items()}
 lib = os.environ.get('NFX_LIB_PATH', 'the tree\'s libnfx.so')
