@@ -309,6 +309,40 @@ NFX_API int nfx_merl_sphere_fwd(const float *dev_xyz, const float *dev_normal, i
                                 const void *dev_table4, const float *dev_lxyz, const float *dev_lweight,
                                 int n_lights, float *dev_rgb /* [n, 3] */, int *dev_idx, void *stream);
 
+/* Rays against a triangle mesh (data_gen/dtu_mvs/surf_from_mvs.py: trimesh's RayMeshIntersector on Embree).
+ *
+ * nfx_mesh_bvh_bytes / nfx_mesh_bvh_build: PURE HOST, no GPU needed.  vertices: float32 [nv, 3], faces: int32 [nf, 3], both on
+ * the host; max_leaf >= 1 = the most triangles of a leaf (max_leaf >= nf: one leaf with every triangle, the brute-force form).
+ * The blob (nfx_mesh_bvh_bytes(nf, max_leaf) bytes, a function of the two counts only; 0 = cannot be built) is written to
+ * host memory: a 32-byte header (magic, version, n_nodes, n_tris, max_leaf), n_nodes + 1 nodes of 32 bytes in depth-first
+ * order (box lo[3], skip link, box hi[3], first triangle; an inner node's first child is index + 1, a skip link is greater
+ * than the node's index and n_nodes at the end), then the triangles reordered leaf by leaf, 48 bytes each, with their index
+ * in `faces`.  Object-median split along the longest axis of the centroids; the same input gives the same bytes.
+ * Zero-area triangles are kept (a triangle with a repeated vertex is never hit); a non-finite vertex or a face index
+ * outside [0, nv) fails with a message.  Copy the blob to the device (16-byte aligned) for the two functions below; they take the header once more
+ * from the HOST (the blob's first 32 bytes) and check it and blob_bytes against each other before anything is launched. */
+NFX_API size_t nfx_mesh_bvh_bytes(int64_t nf, int max_leaf);
+NFX_API int nfx_mesh_bvh_build(const float *vertices, int64_t nv, const int32_t *faces, int64_t nf, int max_leaf,
+                               void *blob, size_t blob_bytes);
+
+/* Closest hit of n rays (intersects_location(..., multiple_hits=False)): rayo, rayd float32 [n, 3], directions of any
+ * length.  t[i] = the smallest t > 0 with rayo + t rayd on a triangle (both faces count), tri[i] = that triangle's index in
+ * `faces`, the smaller index at equal t; a miss, a zero direction and a non-finite ray give t = +inf, tri = -1.  The
+ * watertight test of Woop, Benthin and Wald (2013) in fp32, edge functions redone in fp64 where one is exactly 0; operation
+ * order: csrc/mesh_cast.hip.  Every row is written; a row depends on its own ray and on the triangle set only (not on
+ * max_leaf, the tree or the rest of the launch).  No workspace, no atomics.                                            */
+NFX_API int nfx_mesh_cast(const void *dev_blob, size_t blob_bytes, const void *host_header, const float *dev_rayo,
+                          const float *dev_rayd, int64_t n, float *dev_t, int *dev_tri, void *stream);
+
+/* Light visibility against the mesh (surf_from_mvs.py:gen_lvis), shadow rays made on chip: for row i and light l,
+ * dir = (lxyz[l] - xyz[i]) / |lxyz[l] - xyz[i]|, origin = xyz[i] + eps dir, and
+ * lvis[i, l] = alpha[i] if normal[i] . dir > 0 and the ray hits no triangle at t > 0, else 0 (a row with alpha 0 and a
+ * pair with normal . dir <= 0 are 0 without a traversal, whatever else they hold).  xyz, normal [n, 3], alpha [n],
+ * lxyz [n_lights, 3], lvis [n, n_lights] float32, every element written; any n_lights >= 1.  No workspace, no atomics. */
+NFX_API int nfx_mesh_lvis(const void *dev_blob, size_t blob_bytes, const void *host_header, const float *dev_xyz,
+                          const float *dev_normal, const float *dev_alpha, int64_t n, const float *dev_lxyz,
+                          int n_lights, float eps, float *dev_lvis, void *stream);
+
 /* Rusinkiewicz coordinates (phi_d, theta_h, theta_d), util/geom.py:152-192. a,b [n,3]. */
 NFX_API int nfx_dir2rusink(const float *dev_a, const float *dev_b, int64_t n, float *dev_rusink,
                    void *stream);

@@ -42,6 +42,11 @@ int nfx_launch_brdf_sphere(const float* xyz, const float* normal, long long n, c
 int nfx_launch_merl_query(const void* table4, const float* rusink, long long n, float* rgb, int* idx, hipStream_t st);
 int nfx_launch_merl_sphere(const float* xyz, const float* normal, long long n, const float* cam3, const void* table4, const float* lxyz,
                            const float* lweight, int n_lights, float* rgb, int* idx, hipStream_t st);
+// ---- mesh_cast.hip (blob: mesh_bvh.hpp; the counts are the checked header's)
+int nfx_launch_mesh_cast(const void* blob, int n_nodes, int n_tris, const float* rayo, const float* rayd, long long n, float* t, int* tri,
+                         hipStream_t st);
+int nfx_launch_mesh_lvis(const void* blob, int n_nodes, int n_tris, const float* xyz, const float* normal, const float* alpha, long long n,
+                         const float* lxyz, int n_lights, float eps, float* lvis, hipStream_t st);
 // ---- loss.hip
 int nfx_launch_pair_loss(int bwd, const nfx_loss_term* terms, int n_terms, const float* alpha, float bg, long long n, float* loss,
                          const float* dloss, hipStream_t st);

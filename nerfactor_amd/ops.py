@@ -796,6 +796,64 @@ def merl_sphere_fwd(xyz, normal, cam, table, lxyz, lweight, return_idx=False):
     return (rgb, idx) if return_idx else rgb
 
 
+def mesh_bvh_build(vertices, faces, max_leaf=4):
+    """uint8 host array: the BVH blob of a triangle mesh (nfx_mesh_bvh_build; layout in include/nfx.h).  Pure host code, no GPU
+    needed.  vertices float32 [nv, 3], faces int32 [nf, 3]; a non-finite vertex or a face index out of range raises."""
+    v = np.ascontiguousarray(vertices, dtype=np.float32)
+    f = np.ascontiguousarray(faces, dtype=np.int32)
+    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+        raise _capi.NfxError("mesh_bvh_build: vertices [nv, 3] and faces [nf, 3] are expected, got %s and %s" % (v.shape, f.shape))
+    size = lib.nfx_mesh_bvh_bytes(f.shape[0], int(max_leaf))
+    if size == 0:
+        raise _capi.NfxError("mesh_bvh_build: %d triangles with max_leaf %d cannot be built" % (f.shape[0], max_leaf))
+    blob = np.zeros(size // 16 + 1, dtype=np.complex128).view(np.uint8)[:size]     # 16-byte aligned
+    check(lib.nfx_mesh_bvh_build(v.ctypes.data, v.shape[0], f.ctypes.data, f.shape[0], int(max_leaf), blob.ctypes.data, size),
+          'nfx_mesh_bvh_build')
+    return blob
+
+
+def _mesh_blob(blob, header, who):
+    if not isinstance(blob, torch.Tensor) or not blob.is_cuda or blob.dtype != torch.uint8 or not blob.is_contiguous():
+        raise _capi.NfxError("%s: the BVH blob must be a contiguous CUDA/ROCm uint8 tensor" % who)
+    header = np.ascontiguousarray(header, dtype=np.uint8)
+    if header.size != 32:
+        raise _capi.NfxError("%s: the host header is the blob's first 32 bytes" % who)
+    return blob, header
+
+
+def mesh_cast(blob, header, rayo, rayd):
+    """(t[n], tri[n] int32): the closest hit of every ray with the mesh of a BVH blob on the device (`header`: its first 32
+    bytes on the host); t = +inf and tri = -1 for a miss, a zero direction or a non-finite ray (nfx_mesh_cast)."""
+    blob, header = _mesh_blob(blob, header, 'mesh_cast')
+    rayo = _dev(rayo, 'rayo', (None, 3))
+    n = rayo.shape[0]
+    rayd = _dev(rayd, 'rayd', (n, 3))
+    t = torch.empty((n,), dtype=torch.float32, device=rayo.device)
+    tri = torch.empty((n,), dtype=torch.int32, device=rayo.device)
+    check(lib.nfx_mesh_cast(_ptr(blob), blob.numel(), header.ctypes.data, _ptr(rayo), _ptr(rayd), n, _ptr(t), _ptr(tri), _stream()),
+          'nfx_mesh_cast')
+    return t, tri
+
+
+def mesh_lvis(blob, header, xyz, normal, alpha, lxyz, eps, out=None):
+    """lvis[n, L]: alpha where the light is in front of the surface (normal . dir > 0) and the shadow ray from
+    xyz + eps dir hits nothing, else 0; the rays are made in the kernel (nfx_mesh_lvis)."""
+    blob, header = _mesh_blob(blob, header, 'mesh_lvis')
+    xyz = _dev(xyz, 'xyz', (None, 3))
+    n = xyz.shape[0]
+    normal = _dev(normal, 'normal', (n, 3))
+    alpha = _dev(alpha, 'alpha', (n,))
+    lxyz = _dev(lxyz, 'lxyz', (None, 3))
+    nl = lxyz.shape[0]
+    if out is None:
+        out = torch.empty((n, nl), dtype=torch.float32, device=xyz.device)
+    elif not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.shape != (n, nl):
+        raise _capi.NfxError("mesh_lvis: `out` must be a contiguous CUDA float32 [%d, %d] tensor" % (n, nl))
+    check(lib.nfx_mesh_lvis(_ptr(blob), blob.numel(), header.ctypes.data, _ptr(xyz), _ptr(normal), _ptr(alpha), n, _ptr(lxyz), nl,
+                            float(eps), _ptr(out), _stream()), 'nfx_mesh_lvis')
+    return out
+
+
 def _shade_common(xyz, cam, normal, albedo, rough, spec, lvis, lxyz, lareas, lvis_row=None):
     xyz = _dev(xyz, 'xyz', (None, 3))
     n = xyz.shape[0]
