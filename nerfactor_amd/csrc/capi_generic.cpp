@@ -37,7 +37,7 @@ static int layer_table(int d_in, int n_layers, const int* widths, const int* ski
 static void set_pitches(nfx::generic::Args* a) {
     int widest = 1;
     for (int i = 0; i < a->n_layers; ++i) widest = a->layer[i].n_tiles > widest ? a->layer[i].n_tiles : widest;
-    const int elem = a->f32 ? 4 : 2;                         // (f32 = the prec: 0 bf16, else fp32 activations)
+    const int elem = a->mode ? 4 : 2;                        // (NFX_PREC_BF16 = 0; the other two keep fp32 activations)
     a->x_pitch = (a->d_in + 63) / 64 * 64 * elem + 16;       // whole k-groups (64 features) per row
     a->h_pitch = (widest + 1) / 2 * 64 * elem + 16;
 }
@@ -47,8 +47,8 @@ static int check_prec(int prec, const char* who) {
     return NFX_OK;
 }
 static_assert(NFX_PREC_BF16 == 0 && NFX_PREC_FP32 == 1 && NFX_PREC_FP32_NATIVE == 2, "= nfx::generic::kBf16 / kX3 / kNative (mlp_generic.hip)");
-static bool wide(int prec) { return prec != NFX_PREC_BF16; }      // fp32 activations / workspace, 2-KiB fragments
-static size_t frag_bytes(int prec) { return wide(prec) ? 2048 : 1024; }
+static bool fp32_data(int prec) { return prec != NFX_PREC_BF16; }      // fp32 activations / workspace, 2-KiB fragments
+static size_t frag_bytes(int prec) { return fp32_data(prec) ? 2048 : 1024; }
 static float bf16_to_f32(uint16_t h) {
     const uint32_t u = (uint32_t)h << 16;
     float f;
@@ -64,6 +64,28 @@ static void put(void* frag, int prec, int lane, int i, float v) {
         static_cast<uint16_t*>(frag)[lane * 8 + i] = hi;
         static_cast<uint16_t*>(frag)[512 + lane * 8 + i] = nfx::pack::f32_to_bf16_rne(v - bf16_to_f32(hi));
     } else static_cast<uint16_t*>(frag)[lane * 8 + i] = nfx::pack::f32_to_bf16_rne(v);
+}
+// a whole fragment: lane (m = lane & 31, g = lane >> 5) holds k = 8 g + j, j = 0 .. 7, of A row m; value_of(m, k) is the
+// matrix element there, 0 where the fragment reaches past the matrix.  Every element of the fragment is WRITTEN, pad zeros
+// included; the packers' memset of the blob is still what zeroes the whole pad fragments, which no call here visits.
+template <class F>
+static void fill_fragment(void* frag, int prec, F value_of) {
+    for (int lane = 0; lane < 64; ++lane)
+        for (int j = 0; j < 8; ++j) put(frag, prec, lane, j, value_of(lane & 31, 8 * (lane >> 5) + j));
+}
+// the fields the forward's and the backward's launch share (a.layer is filled by the caller's layer table)
+static void fill_args(nfx::generic::Args& a, const float* x, int64_t n, int ld_x, int d_in, int n_layers, const void* blob, int n_bias,
+                      int n_frags, int prec) {
+    a.x = x;
+    a.n = n;
+    a.ld_x = ld_x;
+    a.d_in = d_in;
+    a.biases = static_cast<const float*>(blob);
+    a.weights = static_cast<const char*>(blob) + (size_t)n_bias * 4;
+    a.n_layers = n_layers;
+    a.n_frags = n_frags;
+    a.mode = prec;
+    set_pitches(&a);
 }
 
 size_t nfx_mlp_generic_packed_bytes(int d_in, int n_layers, const int* widths, const int* skip_input, int prec) {
@@ -90,9 +112,8 @@ int nfx_mlp_generic_pack(const float* const* kernels, const float* const* biases
     for (int i = 0; i < n_layers; ++i) {
         REQUIRE(kernels[i] && biases[i], "nfx_mlp_generic_pack: layer %d null", i);
         const nfx::generic::Layer& L = t[i];
-        const int prev = i == 0 ? 0 : widths[i - 1];          // rows [0, prev): the previous layer's output
-        const int n_in = prev + (L.ks_x ? d_in : 0);          // then the network input (mlp.py:48: y first)
-        (void)n_in;
+        // rows [0, prev) of the kernel: the previous layer's output, then the network input (mlp.py:48: y first)
+        const int prev = i == 0 ? 0 : widths[i - 1];
         for (int tl = 0; tl < L.n_tiles; ++tl)
             for (int s = 0; s < L.ks_h + L.ks_x; ++s) {
                 // stream order of a layer: k-GROUP outer, output tile inner (the kernel reads a group's B operand once
@@ -101,15 +122,10 @@ int nfx_mlp_generic_pack(const float* const* kernels, const float* const* biases
                 char* frag = w + ((size_t)L.w_off + ((size_t)kg * L.n_tiles + tl) * nfx::generic::kGroup + j4) * fb;
                 const bool from_x = s >= L.ks_h;
                 const int base = from_x ? prev : 0, feat0 = 16 * (from_x ? s - L.ks_h : s), limit = from_x ? d_in : prev;
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int m = lane & 31, g = lane >> 5, col = 32 * tl + m;
-                    if (col >= L.n_out) continue;
-                    for (int j = 0; j < 8; ++j) {
-                        const int f = feat0 + 8 * g + j;
-                        if (f >= limit) continue;
-                        put(frag, prec, lane, j, kernels[i][(size_t)(base + f) * L.n_out + col]);
-                    }
-                }
+                fill_fragment(frag, prec, [&](int m, int k) {         // A row = output feature, k = input feature
+                    const int col = 32 * tl + m, f = feat0 + k;
+                    return col < L.n_out && f < limit ? kernels[i][(size_t)(base + f) * L.n_out + col] : 0.f;
+                });
             }
         for (int c = 0; c < L.n_out; ++c) b[L.b_off + c] = biases[i][c];
     }
@@ -130,19 +146,10 @@ int nfx_mlp_generic_fwd(const float* x, int64_t n, int ld_x, int d_in, int n_lay
     REQUIRE(x && blob && y, "nfx_mlp_generic_fwd: null pointer");
     REQUIRE(ld_x >= d_in && ld_y >= col0 + widths[n_layers - 1] && col0 >= 0, "nfx_mlp_generic_fwd: bad leading dimensions");
     if ((uintptr_t)blob & 15) return nfx_fail(NFX_EALIGN, "nfx_mlp_generic_fwd: blob must be 16-byte aligned");
-    a.x = x;
-    a.n = n;
-    a.ld_x = ld_x;
-    a.d_in = d_in;
-    a.biases = static_cast<const float*>(blob);
-    a.weights = static_cast<const char*>(blob) + (size_t)nb * 4;
+    fill_args(a, x, n, ld_x, d_in, n_layers, blob, nb, nf, prec);
     a.y = y;
     a.ld_y = ld_y;
     a.col0 = col0;
-    a.n_layers = n_layers;
-    a.n_frags = nf;
-    a.f32 = prec;
-    set_pitches(&a);
     rc = nfx_launch_mlp_generic(&a, 8 * nfx_option_int("nerf_blocks", 256), (hipStream_t)stream);
     if (rc < 0) return nfx_fail(NFX_ENOSUP, "nfx_mlp_generic_fwd: this shape needs %d bytes of LDS per wave (160 KiB per CU): narrower layers or a smaller input", -rc);
     return nfx_hip_result(rc, "mlp_generic_fwd");
@@ -206,6 +213,9 @@ int wgrad_splits(long long tiles, int n_jobs) {
     return s < 1 ? 1 : (int)s;
 }
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+// the workspace's activations and gradients, [tiles + 1][feat_rows][32] (the spare tile: for the waves of the last workgroup
+// that have no row tile of their own, mlp_generic.hip); the weight-gradient partials follow
+size_t workspace_act_bytes(long long tiles, int feat_rows, int prec) { return align256((size_t)(tiles + 1) * feat_rows * (fp32_data(prec) ? 128 : 64)); }
 }  // namespace
 
 size_t nfx_mlp_generic_train_packed_bytes(int d_in, int n_layers, const int* widths, const int* skip_input, int prec) {
@@ -235,8 +245,7 @@ int nfx_mlp_generic_pack_train(const float* const* kernels, const float* const* 
         const int ks_o_pad = nfx::generic::pad_group(ks_o);
         // a layer's transposed fragments: the input-gradient tiles FIRST (tile-major: they read dZ before the hidden
         // tiles overwrite it in place), then the hidden tiles k-group outer / tile inner like the forward
-        const int nx = m_in - mh, kgo = ks_o_pad / nfx::generic::kGroup;
-        (void)kgo;
+        const int nx = m_in - mh;
         for (int mt = 0; mt < m_in; ++mt)
             for (int s = 0; s < ks_o; ++s) {
                 const bool from_x = mt >= mh;
@@ -245,14 +254,10 @@ int nfx_mlp_generic_pack_train(const float* const* kernels, const float* const* 
                                           : (size_t)nx * ks_o_pad + ((size_t)kg * mh + mt) * nfx::generic::kGroup + j4;
                 char* frag = wt + ((size_t)p.b[i].wt_off + idx) * fb;
                 const int base = from_x ? prev : 0, feat0 = 32 * (from_x ? mt - mh : mt), limit = from_x ? d_in : prev;
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int f = feat0 + (lane & 31), g = lane >> 5;       // A row = input feature, k = output feature
-                    if (f >= limit) continue;
-                    for (int j = 0; j < 8; ++j) {
-                        const int o = 16 * s + 8 * g + j;
-                        if (o < L.n_out) put(frag, prec, lane, j, kernels[i][(size_t)(base + f) * L.n_out + o]);
-                    }
-                }
+                fill_fragment(frag, prec, [&](int m, int k) {         // A row = input feature, k = output feature
+                    const int f = feat0 + m, o = 16 * s + k;
+                    return f < limit && o < L.n_out ? kernels[i][(size_t)(base + f) * L.n_out + o] : 0.f;
+                });
             }
     }
     return NFX_OK;
@@ -262,8 +267,7 @@ size_t nfx_mlp_generic_bwd_workspace_bytes(int64_t n, int d_in, int n_layers, co
     BwdPlan p;
     if (n < 0 || !widths || check_prec(prec, "nfx_mlp_generic_bwd_workspace_bytes") || bwd_plan(d_in, n_layers, widths, skip_input, nullptr, &p)) return 0;
     const long long tiles = (n + 31) / 32;
-    // (tiles + 1: a spare tile for the waves of the last workgroup that have no row tile of their own, mlp_generic.hip)
-    return align256((size_t)(tiles + 1) * p.feat_rows * (wide(prec) ? 128 : 64)) + (size_t)wgrad_splits(tiles, p.n_jobs) * p.slice * 4 + 256;
+    return workspace_act_bytes(tiles, p.feat_rows, prec) + (size_t)wgrad_splits(tiles, p.n_jobs) * p.slice * 4 + 256;
 }
 
 int nfx_mlp_generic_bwd(const float* x, int64_t n, int ld_x, int d_in, int n_layers, const int* widths, const int* acts,
@@ -294,14 +298,6 @@ int nfx_mlp_generic_bwd(const float* x, int64_t n, int ld_x, int d_in, int n_lay
     memset(&ba, 0, sizeof ba);
     memset(&wa, 0, sizeof wa);
     const long long tiles = (n + 31) / 32;
-    ba.f.x = x;
-    ba.f.n = n;
-    ba.f.ld_x = ld_x;
-    ba.f.d_in = d_in;
-    ba.f.biases = static_cast<const float*>(train_blob);
-    ba.f.weights = static_cast<const char*>(train_blob) + (size_t)p.n_bias * 4;
-    ba.f.n_layers = n_layers;
-    ba.f.n_frags = p.n_frags;
     // layer 0's transposed tiles (all of them input-gradient tiles) end the stream: not walked when dx is not wanted
     ba.stream_frags = p.n_frags + p.n_tfrags - (dx ? 0 : (d_in + 31) / 32 * nfx::generic::pad_group(2 * p.layer[0].n_tiles));
     ba.dy = dy;
@@ -322,15 +318,14 @@ int nfx_mlp_generic_bwd(const float* x, int64_t n, int ld_x, int d_in, int n_lay
     wa.map = nfx_option_int("wgrad_map", 1);
     wa.slice = p.slice;
     wa.dw_total = p.dw_total;
-    wa.partial = reinterpret_cast<float*>(ba.ws + align256((size_t)(tiles + 1) * p.feat_rows * (wide(prec) ? 128 : 64)));
+    wa.partial = reinterpret_cast<float*>(ba.ws + workspace_act_bytes(tiles, p.feat_rows, prec));
     for (int i = 0; i < n_layers; ++i) {
         ba.f.layer[i] = wa.layer[i] = p.layer[i];
         ba.b[i] = wa.b[i] = p.b[i];
         wa.dw[i] = dkernels ? dkernels[i] : nullptr;
         wa.db[i] = dkernels ? dbiases[i] : nullptr;
     }
-    ba.f.f32 = prec;
-    set_pitches(&ba.f);
+    fill_args(ba.f, x, n, ld_x, d_in, n_layers, train_blob, p.n_bias, p.n_frags, prec);      // (after the layer table: set_pitches reads it)
     rc = nfx_launch_mlp_generic_bwd(&ba, &wa, 8 * nfx_option_int("nerf_blocks", 256), (hipStream_t)stream);
     if (rc < 0) return nfx_fail(NFX_ENOSUP, "nfx_mlp_generic_bwd: this shape needs %d bytes of LDS per wave (160 KiB per CU): narrower layers or a smaller input", -rc);
     return nfx_hip_result(rc, "mlp_generic_bwd");

@@ -1,55 +1,54 @@
-// mlp_generic.hip — the network shapes the tuned kernels do NOT cover (round 4): any mlp.Network the reference can build
-// (nerfactor/networks/mlp.py:24-50: widths, activations, skip_at anywhere; nerfactor/models/nerf.py:53-90: mlp_width,
-// enc_depth, use_views = False, pos_enc = False) evaluated by ONE runtime-shaped fused kernel, forward only.
+// mlp_generic.hip — the network shapes the tuned kernels do NOT cover, and every precision = fp32 training step: any
+// mlp.Network the reference can build (nerfactor/networks/mlp.py:24-50: widths, activations, skip_at anywhere;
+// nerfactor/models/nerf.py:53-90: mlp_width, enc_depth, use_views = False, pos_enc = False) through runtime-shaped fused
+// kernels: forward (mlp_generic_kernel), backward (mlp_generic_bwd_kernel, mlp_generic_wgrad_kernel and one ordered
+// reduction) and the Embedder (embedder.py:23-47, with the point generation o + d z folded in) as kernels of its own.
 //
 // The tuned kernels (nerf_mlp_v6.hip, mlp128.hip, lvis_v2.hip) are compile-time specialisations of one architecture
-// each — register-resident activations, packed weight streams.  This one trades their speed for generality and keeps
-// their arithmetic class: bf16 operands, fp32 accumulation and bias, one v_mfma_f32_32x32x16_bf16 per
-// (32 outputs x 32 rows x 16 inputs), transposed formulation H^T = W^T X^T (mlp_engine.hpp):
-//   * one wave = 32 rows, no workgroup-level synchronisation at all (waves are independent);
-//   * activations live in the wave's own LDS area (sized from the network's real widths) as ROW-MAJOR bf16 — the network
-//     input (kept for the skip concatenations) and ONE hidden buffer: a layer accumulates ALL its output tiles in
-//     registers (k-group outer, tile inner: the B operand of a group — a plain ds_read_b128 of the lane's row — is read
-//     once for all tiles) and only then overwrites its input with its output, four 8-byte stores per lane and tile;
+// each — register-resident activations, packed weight streams.  These trade their speed for generality and keep their
+// arithmetic class: fp32 accumulation and bias, 32 x 32 MFMA tiles, transposed formulation H^T = W^T X^T (mlp_engine.hpp):
+//   * one wave = 32 rows; the waves of a workgroup share nothing but the weight ring (Ring below);
+//   * activations live in the wave's own LDS area (sized from the network's real widths), ROW-MAJOR — the network input
+//     (kept for the skip concatenations) and ONE hidden buffer: a layer accumulates ALL its output tiles in registers
+//     (k-group outer, tile inner: the B operand of a group, 8 consecutive features of the lane's row, is read once for
+//     all tiles) and only then overwrites its input with its output, four stores per lane and tile;
 //   * weights are packed on the host in LOGICAL feature order (no permutation is needed: the operand comes from LDS,
-//     not from the previous tile's accumulators) as 1-KiB A fragments, ONE stream in consumption order that each wave
-//     pulls through its own LDS ring with the DMA path, three groups of four fragments ahead of its MFMAs;
+//     not from the previous tile's accumulators) as A fragments of one k-step, ONE stream in consumption order pulled
+//     through an LDS ring with the DMA path, groups of four fragments ahead of the MFMAs;
 //   * the layer table (input widths, tiles, activation, fragment and bias offsets) is a kernel argument.
 // Limits: network input <= 576 features, hidden widths <= 512, <= 16 layers, output <= 512 (and the wave's two activation rows
 // beside the weight ring within the 160 KiB of LDS: checked per launch).
-// nfx_embed is the Embedder (embedder.py:23-47) as its own kernel, with the point generation o + d z folded in.
 //
-// Backward (mlp_generic_bwd_kernel + mlp_generic_wgrad_kernel + one ordered reduction; mlp_generic.hpp has the
-// workspace layout): the same wave re-computes its 32 rows' forward, turns dLoss/dy into the output-layer gradient and
-// walks the layers back with the TRANSPOSED weight fragments — dH^T = W dZ^T is the forward's loop with another weight
-// stream — multiplying by the activation's derivative taken from the stored bf16 outputs.  Every layer's input and
-// gradient go to the workspace through the transposing LDS read (tr16.hpp), 1 KiB contiguous per 16 features; the
-// weight-gradient kernel then needs no LDS at all: one wave per (64 x 64 block of dW, row split), all MFMA operands
-// 16-byte loads.  Deterministic: fixed split count per problem shape, ordered reductions, no atomics.
+// Backward (mlp_generic.hpp has the workspace layout): the same wave re-computes its 32 rows' forward, turns dLoss/dy
+// into the output-layer gradient and walks the layers back with the TRANSPOSED weight fragments — dH^T = W dZ^T is the
+// forward's loop with another weight stream — multiplying by the activation's derivative taken from the stored outputs.
+// Every layer's input and gradient go to the workspace feature-major (store_blocked), 1 KiB contiguous per 16 (bf16) or 8
+// (fp32) features; the weight-gradient kernel then needs no LDS at all: one wave per (64 x 64 block of dW, row split),
+// all MFMA operands 16-byte loads.  Deterministic: fixed split count per problem shape, ordered reductions, no atomics.
 //
-// NFX_PREC_FP32_NATIVE: the same kernels instantiated with fp32 activations in LDS, fp32 fragments (2 KiB per
-// k-step) and the native fp32 matrix instruction v_mfma_f32_32x32x2_f32 — eight per k-step, k = 8 g + i on both
-// operands — i.e. the reference's own arithmetic (trainvali.py:273-285 differentiates in fp32), forward AND backward,
-// for any shape including the shipped ones.  157 TFLOP/s is that instruction's peak; at one wave per SIMD its 64-cycle
-// issue hides the loop's scalar work, so this path is MFMA-bound where the bf16 one is issue-bound.
-//
-// NFX_PREC_FP32 (round 5): fp32-class arithmetic on the bf16 matrix pipe, the hi / lo operand pairs of mlp_x3.hpp in
-// the runtime-shaped kernels.  Activations, gradients and the workspace stay fp32 exactly as in the native mode; a
-// weight fragment is the same 2 KiB, pre-split by the packer into [hi plane | lo plane] (hi = bf16(w), lo = bf16(w - hi),
-// lane order of the bf16 fragment: the 8 consecutive k of a lane are the same in both instructions), the B operand — 8
-// consecutive fp32 features of the lane's row — is split in registers once per k-group for all output tiles, and a
-// k-step is three v_mfma_f32_32x32x16_bf16 (a_lo b_hi + a_hi b_lo + a_hi b_hi) = 96 matrix-pipe cycles instead of the
-// 512 of eight fp32 instructions.  Operands carry 16 significant bits: gradients within 1e-3 of the reference's
-// (tests/test_gpu_reference_grads.py), at a fifth of the native mode's matrix time.
+// Three operand modes (P<M>, Frag<M>), one translation unit each:
+//   kBf16   (NFX_PREC_BF16): bf16 activations and 1-KiB fragments, one v_mfma_f32_32x32x16_bf16 per k-step (32 outputs x
+//           32 rows x 16 inputs).  Issue-bound.
+//   kNative (NFX_PREC_FP32_NATIVE): fp32 activations in LDS, fp32 fragments (2 KiB per k-step) and v_mfma_f32_32x32x2_f32 —
+//           eight per k-step, k = 8 g + i on both operands — i.e. the reference's own arithmetic (trainvali.py:273-285
+//           differentiates in fp32), forward AND backward, for any shape including the shipped ones.  157 TFLOP/s is that
+//           instruction's peak; at one wave per SIMD its 64-cycle issue hides the loop's scalar work: MFMA-bound.
+//   kX3     (NFX_PREC_FP32): fp32-class arithmetic on the bf16 matrix pipe, the hi / lo operand pairs of mlp_x3.hpp.
+//           Activations, gradients and the workspace stay fp32 exactly as in the native mode; a weight fragment is the
+//           same 2 KiB, pre-split by the packer into [hi plane | lo plane] (hi = bf16(w), lo = bf16(w - hi), lane order
+//           of the bf16 fragment: the 8 consecutive k of a lane are the same in both instructions), the B operand is
+//           split in registers once per k-group for all output tiles, and a k-step is three v_mfma_f32_32x32x16_bf16
+//           (a_lo b_hi + a_hi b_lo + a_hi b_hi) = 96 matrix-pipe cycles instead of the 512 of eight fp32 instructions.
+//           Operands carry 16 significant bits: gradients within 1e-3 of the reference's
+//           (tests/test_gpu_reference_grads.py), at a fifth of the native mode's matrix time.
 #include "mlp_engine.hpp"
 #include "lds_dma.hpp"
 #include "mlp_generic.hpp"
 #include "tr16.hpp"
 #include "launchers.hpp"
 
-// This file is compiled three times (build time: one translation unit per operand mode, in parallel): as itself
-// (NFX_GENERIC_TU = 0: the bf16 instantiations, the mode-independent kernels and the C launch entry points) and through
-// mlp_generic_x3.hip / mlp_generic_native.hip (NFX_GENERIC_TU = 1 | 2: the fp32-class / native-fp32 instantiations).
+// Compiled three times (build time: in parallel): as itself (NFX_GENERIC_TU = 0: the bf16 instantiations, the mode-independent
+// kernels, the C launch entry points) and through mlp_generic_x3.hip / mlp_generic_native.hip (1 | 2: fp32-class / native fp32).
 #ifndef NFX_GENERIC_TU
 #define NFX_GENERIC_TU 0
 #endif
@@ -57,10 +56,9 @@
 namespace nfx {
 namespace generic {
 
-// One wave per workgroup (waves are independent: no barrier anywhere).  LDS of a wave: the weight ring, then 32 rows x
-// (x_pitch + h_pitch) bytes — the network input and ONE hidden buffer that every layer updates in place — the pitches
-// sized by the HOST from the network's real widths (Args::x_pitch / h_pitch: features x element size + 16, rows 4 banks
-// apart) — bf16: a 256-wide network keeps 4 waves per CU resident (33.5 KiB each), fp32: 2 (66 KiB).
+// LDS of a workgroup: the weight ring, then per wave 32 rows x (x_pitch + h_pitch) bytes — the pitches sized by the HOST
+// from the network's real widths (Args::x_pitch / h_pitch: features x element size + 16, rows 4 banks apart) — bf16: a
+// 256-wide network keeps 4 waves per CU resident (33.5 KiB each), fp32: 2 (66 KiB).
 // LDS is addressed through address_space(3) pointers THROUGHOUT: a generic pointer that the compiler cannot trace back to
 // the shared array (a select between two buffers is enough) becomes a flat load, which waits on vmcnt — i.e. on the
 // weight ring's look-ahead — before every MFMA.
@@ -70,14 +68,13 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
 
-// What differs between the operand modes M: kBf16: bf16 operands, v_mfma_f32_32x32x16_bf16; kNative: fp32 operands,
-// 8 x v_mfma_f32_32x32x2_f32 per k-step; kX3: the fp32 DATA layout (LDS, workspace, fragment size) of kNative with
-// hi / lo bf16 pairs as MFMA operands, 3 x v_mfma_f32_32x32x16_bf16 per k-step.
-enum : int { kBf16 = 0, kX3 = 1, kNative = 2 };        // = Args::f32 = the C-ABI's NFX_PREC_BF16 / _FP32 / _FP32_NATIVE
+// What differs between the operand modes M in sizes (kX3 has the fp32 DATA layout of kNative); Frag<M> has the operands
+enum : int { kBf16 = 0, kX3 = 1, kNative = 2 };        // = Args::mode = the C-ABI's NFX_PREC_BF16 / _FP32 / _FP32_NATIVE
 template <int M>
 struct P {
     static constexpr bool kF32 = M != kBf16;                  // fp32 activations / workspace / 2-KiB fragments
-    static constexpr int kElem = kF32 ? 4 : 2;                // bytes per activation / weight
+    typedef std::conditional_t<kF32, float, __bf16> Elem;     // an activation in LDS and in the workspace
+    static constexpr int kElem = sizeof(Elem);                // bytes per activation / weight
     static constexpr int kFrag = 32 * 16 * kElem;             // one k-step's A fragment (32 outputs x 16 inputs): 1 or 2 KiB
     static constexpr int kGroupBytes = kGroup * kFrag;
     static constexpr int kPieces = kGroupBytes / 1024;        // DMA pieces per group: 4 or 8
@@ -101,13 +98,12 @@ static_assert(kGroup == 4, "a group = 4 fragments = 4 (bf16) or 8 (fp32 modes) 1
 // cannot rotate its buffers without waiting for the loads it just issued; an LDS slot is only an address.  The stream is
 // circular: behind its last group the ring already fetches the next row tile's first.
 //
-// Round 5, fp32 modes: ONE ring per workgroup of NW waves (NW = 4, 2 or 1: what fits the LDS beside NW activation areas;
-// bf16 keeps NW = 1, see generic_waves).  Round 4 gave
-// every wave its own ring: each wave then issues every 1-KiB DMA piece of the network itself, 4 (bf16) or 8 (fp32 modes)
-// global_load_lds per 4 (12, 32) MFMAs, and at 60-180 cycles of issue per piece (MI355X_MICROARCH.md) the DMA issue, not
-// the matrix pipe, set the pace (bf16: 13 % matrix-pipe busy at 384 TFLOP/s).  The NW waves of a workgroup run the same
-// network on NW different 32-row tiles in lock step — identical control flow, since every trip count comes from the layer
-// table — so a group is fetched ONCE, each wave issuing pieces / NW of it, and consumed by all:
+// fp32 modes: ONE ring per workgroup of NW waves (NW = 4, 2 or 1: what fits the LDS beside NW activation areas; bf16 keeps
+// NW = 1, see generic_waves).  With a ring per wave each wave issues every 1-KiB DMA piece of the network itself, 4 (bf16) or
+// 8 (fp32 modes) global_load_lds per 4 (12, 32) MFMAs, and at 60-180 cycles of issue per piece (MI355X_MICROARCH.md) the DMA
+// issue, not the matrix pipe, sets the pace (bf16: 13 % matrix-pipe busy at 384 TFLOP/s).  The NW waves of a workgroup run
+// the same network on NW different 32-row tiles in lock step — identical control flow, since every trip count comes from
+// the layer table — so a group is fetched ONCE, each wave issuing pieces / NW of it, and consumed by all:
 //   acquire(g): s_waitcnt vmcnt(my pieces of the groups behind g still allowed in flight) ; s_barrier   -> every wave's
 //               pieces of group g have landed AND every wave has finished reading group g - 1 (release below) -> the
 //               slot of g - 1 is refilled right here, with group g - 1 + kRingGroups;
@@ -191,62 +187,93 @@ __device__ __forceinline__ f32x16 mma_x3(const bf16x8& ah, const bf16x8& al, con
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, b.lo, acc, 0, 0, 0);
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, b.hi, acc, 0, 0, 0);
 }
-// One 32 x 32 output tile: acc += W_tile^T [h | x], kg_h groups of four k-steps over the previous layer's output, then
-// kg_x over the network input.  A: the ring; B: 64 consecutive features of the lane's own row in LDS.  Nothing in the
-// loop depends on the k-step but immediate offsets: pad steps multiply zero fragments with whatever finite number the
-// row holds there (the activation area is zeroed once, then only ever holds activations).
-// fp32: a fragment is [half][lane][4 floats] — lane (m, g) holds W[16 s + 8 g + 4 half + r][m] — and MFMA i of a k-step
-// contracts k = 8 g + i on both operands.
+// A k-step's operand in mode M: 8 consecutive k of the lane's row / column, from the workspace (`load`: 8 consecutive rows of
+// one feature), from the lane's own activation row in LDS (`row`: 8 consecutive features) or from a ring slot (`ring`: the
+// lane's 16 + 16 bytes of a packed weight fragment), and the MFMAs of one k-step on two of them.
+template <int M> struct Frag;
+template <> struct Frag<kBf16> {
+    bf16x8 v;
+    __device__ __forceinline__ void load(const char* p) { v = *reinterpret_cast<const bf16x8*>(p); }
+    __device__ __forceinline__ void row(const lds_char* p) { v = *reinterpret_cast<const lds_bf16x8*>(p); }
+    __device__ __forceinline__ void ring(const lds_char* p) { row(p); }
+    typedef Frag FromRing, FromRow;      // (operands straight into registers; kNative defers them)
+    __device__ __forceinline__ void ones() {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = (__bf16)1.0f;
+    }
+    static __device__ __forceinline__ f32x16 mma(const Frag& a, const Frag& b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v, b.v, c, 0, 0, 0); }
+    static __device__ __forceinline__ f32x16 mma_ones(const Frag& one, const Frag& b, f32x16 c) { return mma(one, b, c); }
+};
+template <> struct Frag<kX3> {      // activations (8 consecutive fp32) are split in registers; weights come split from the blob
+    HiLo v;
+    __device__ __forceinline__ void load(const char* p) { v = split8(*reinterpret_cast<const f32x4*>(p), *reinterpret_cast<const f32x4*>(p + 16)); }
+    __device__ __forceinline__ void row(const lds_char* p) { v = split8(*reinterpret_cast<const lds_f32x4*>(p), *reinterpret_cast<const lds_f32x4*>(p + 16)); }
+    __device__ __forceinline__ void ring(const lds_char* p) {      // fragment = [hi plane | lo plane], 1 KiB each, bf16 lane order
+        v.hi = *reinterpret_cast<const lds_bf16x8*>(p);
+        v.lo = *reinterpret_cast<const lds_bf16x8*>(p + 1024);
+    }
+    typedef Frag FromRing, FromRow;      // (operands straight into registers; kNative defers them)
+    __device__ __forceinline__ void ones() {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { v.hi[j] = (__bf16)1.0f; v.lo[j] = (__bf16)0.0f; }
+    }
+    static __device__ __forceinline__ f32x16 mma(const Frag& a, const Frag& b, f32x16 c) { return mma_x3(a.v.hi, a.v.lo, b.v, c); }
+    static __device__ __forceinline__ f32x16 mma_ones(const Frag& one, const Frag& b, f32x16 c) {      // (1 has no lo half)
+        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(one.v.hi, b.v.lo, c, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(one.v.hi, b.v.hi, c, 0, 0, 0);
+    }
+};
+// fp32: a fragment is [half][lane][4 floats], lane (m, g) holds W[16 s + 8 g + 4 half + r][m]; MFMA i contracts k = 8 g + i
+template <> struct Frag<kNative> {
+    f32x4 lo, hi;
+    __device__ __forceinline__ void load(const char* p) { lo = *reinterpret_cast<const f32x4*>(p); hi = *reinterpret_cast<const f32x4*>(p + 16); }
+    __device__ __forceinline__ void row(const lds_char* p) { lo = *reinterpret_cast<const lds_f32x4*>(p); hi = *reinterpret_cast<const lds_f32x4*>(p + 16); }
+    __device__ __forceinline__ void ring(const lds_char* p) { lo = *reinterpret_cast<const lds_f32x4*>(p); hi = *reinterpret_cast<const lds_f32x4*>(p + 1024); }
+    __device__ __forceinline__ void ones() { lo = hi = f32x4{1.f, 1.f, 1.f, 1.f}; }
+    static __device__ __forceinline__ f32x16 mma(const Frag& a, const Frag& b, f32x16 c) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.lo[i], b.lo[i], c, 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.hi[i], b.hi[i], c, 0, 0, 0);
+        return c;
+    }
+    static __device__ __forceinline__ f32x16 mma_ones(const Frag& one, const Frag& b, f32x16 c) { return mma(one, b, c); }
+    // A slot's fragment (tile_mma: the row's operand too) is read right before its eight MFMAs, not a group at a time: these
+    // two only note where it lies.  They exist for the instruction order alone — with plain Frag operands the eight native
+    // forward and backward kernels change (profiles/generic_operand/code_objects.txt, form 1).
+    struct FromRing { const lds_char* p; __device__ __forceinline__ void ring(const lds_char* q) { p = q; } };
+    struct FromRow { const lds_char* p; __device__ __forceinline__ void row(const lds_char* q) { p = q; } };
+    static __device__ __forceinline__ f32x16 mma(const FromRing& a, const Frag& b, f32x16 c) { Frag f; f.ring(a.p); return mma(f, b, c); }
+    static __device__ __forceinline__ f32x16 mma(const FromRing& a, const FromRow& b, f32x16 c) { Frag fa, fb; fa.ring(a.p); fb.row(b.p); return mma(fa, fb, c); }
+};
+// One 32 x 32 output tile: acc += W_tile^T [h | x], kg_h groups of four k-steps over the previous layer's output, then kg_x
+// over the network input.  A: the ring; B: 64 consecutive features of the lane's own row in LDS.  Nothing in the loop depends
+// on the k-step but immediate offsets: pad steps multiply zero fragments with whatever finite number the row holds there.
 template <int M, int NW>
 __device__ __forceinline__ f32x16 tile_mma(f32x16 acc, Ring<M, NW>& w, int kg_h, int kg_x, const lds_char* hsrc, const lds_char* xsrc) {
     for (int gi = 0; gi < kg_h + kg_x; ++gi) {
         const lds_char* bsrc = gi < kg_h ? hsrc + gi * (kGroup * P<M>::kStep) : xsrc + (gi - kg_h) * (kGroup * P<M>::kStep);
         w.acquire();
         const lds_char* grp = w.group();
-        if constexpr (M == kBf16) {
-            bf16x8 af[kGroup], bf[kGroup];
+        typename Frag<M>::FromRing a[kGroup];
+        typename Frag<M>::FromRow b[kGroup];
 #pragma unroll
-            for (int j = 0; j < kGroup; ++j) {
-                af[j] = *reinterpret_cast<const lds_bf16x8*>(grp + j * 1024);
-                bf[j] = *reinterpret_cast<const lds_bf16x8*>(bsrc + j * 32);
-            }
-#pragma unroll
-            for (int j = 0; j < kGroup; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[j], bf[j], acc, 0, 0, 0);
-        } else if constexpr (M == kX3) {      // fragment = [hi plane | lo plane], 1 KiB each, bf16 lane order
-            bf16x8 ah[kGroup], al[kGroup];
-            HiLo b[kGroup];
-#pragma unroll
-            for (int j = 0; j < kGroup; ++j) {
-                ah[j] = *reinterpret_cast<const lds_bf16x8*>(grp + j * 2048);
-                al[j] = *reinterpret_cast<const lds_bf16x8*>(grp + j * 2048 + 1024);
-                {
-                    const f32x4 f0 = *reinterpret_cast<const lds_f32x4*>(bsrc + j * 64), f1 = *reinterpret_cast<const lds_f32x4*>(bsrc + j * 64 + 16);
-                    b[j] = split8(f0, f1);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < kGroup; ++j) acc = mma_x3(ah[j], al[j], b[j], acc);
-        } else {
-#pragma unroll
-            for (int j = 0; j < kGroup; ++j) {
-                const f32x4 a0 = *reinterpret_cast<const lds_f32x4*>(grp + j * 2048), a1 = *reinterpret_cast<const lds_f32x4*>(grp + j * 2048 + 1024);
-                const f32x4 b0 = *reinterpret_cast<const lds_f32x4*>(bsrc + j * 64), b1 = *reinterpret_cast<const lds_f32x4*>(bsrc + j * 64 + 16);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[i], b0[i], acc, 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[i], b1[i], acc, 0, 0, 0);
-            }
+        for (int j = 0; j < kGroup; ++j) {
+            a[j].ring(grp + j * P<M>::kFrag);
+            b[j].row(bsrc + j * P<M>::kStep);
         }
+#pragma unroll
+        for (int j = 0; j < kGroup; ++j) acc = Frag<M>::mma(a[j], b[j], acc);
         // the slot is refilled only after every read of it has RETURNED (the compiler may sink MFMAs below this point,
         // not memory operations above it); the wait overlaps the first MFMAs of the group
         w.release();
     }
     return acc;
 }
-// A whole layer, k-group OUTER and output tile INNER: the four B operands of a group are read from LDS once and swept
-// over the NT tiles' accumulators (the stream holds a layer's fragments in exactly this order), so a hidden layer costs
-// 1 + 1/NT LDS reads per MFMA instead of 2 — and because every output tile is complete before any is written, the layer's
-// output can overwrite its input IN PLACE: one hidden buffer per wave instead of two.
+// A whole layer, k-group OUTER and output tile INNER: the four B operands of a group are read from LDS once (kX3: and
+// split once, 24 VALU per k-step) and swept over the NT tiles' accumulators (the stream holds a layer's fragments in
+// exactly this order), so a hidden layer costs 1 + 1/NT LDS reads per MFMA instead of 2 — and because every output tile is
+// complete before any is written, the layer's output can overwrite its input IN PLACE: one hidden buffer per wave instead of two.
 // `tile_done(t, acc)` is called once per output tile after the last k-group (the accumulators never leave this function:
 // handed out by reference they end up in scratch memory).
 template <int M, int NW, int NT, bool ROLLED, class TileDone>
@@ -258,64 +285,19 @@ __device__ __forceinline__ void layer_mma(Ring<M, NW>& w, int kg_h, int kg_x, co
         for (int q = 0; q < 16; ++q) acc[t][q] = 0.f;
     for (int gi = 0; gi < kg_h + kg_x; ++gi) {
         const lds_char* bsrc = gi < kg_h ? hsrc + gi * (kGroup * P<M>::kStep) : xsrc + (gi - kg_h) * (kGroup * P<M>::kStep);
-        if constexpr (M == kBf16) {
-            bf16x8 bf[kGroup];
+        Frag<M> b[kGroup];
 #pragma unroll
-            for (int j = 0; j < kGroup; ++j) bf[j] = *reinterpret_cast<const lds_bf16x8*>(bsrc + j * 32);
+        for (int j = 0; j < kGroup; ++j) b[j].row(bsrc + j * P<M>::kStep);
 #pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                w.acquire();
-                const lds_char* grp = w.group();
-                bf16x8 af[kGroup];
+        for (int t = 0; t < NT; ++t) {
+            w.acquire();
+            const lds_char* grp = w.group();
+            typename Frag<M>::FromRing a[kGroup];
 #pragma unroll
-                for (int j = 0; j < kGroup; ++j) af[j] = *reinterpret_cast<const lds_bf16x8*>(grp + j * 1024);
+            for (int j = 0; j < kGroup; ++j) a[j].ring(grp + j * P<M>::kFrag);
 #pragma unroll
-                for (int j = 0; j < kGroup; ++j) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[j], bf[j], acc[t], 0, 0, 0);
-                w.release();     // (every read of the slot has returned)
-            }
-        } else if constexpr (M == kX3) {
-            // the group's B operand is split ONCE (24 VALU per k-step) for all NT tiles; the A pairs come split from the blob
-            HiLo b[kGroup];
-#pragma unroll
-            for (int j = 0; j < kGroup; ++j) {
-                const f32x4 f0 = *reinterpret_cast<const lds_f32x4*>(bsrc + j * 64), f1 = *reinterpret_cast<const lds_f32x4*>(bsrc + j * 64 + 16);
-                b[j] = split8(f0, f1);
-            }
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                w.acquire();
-                const lds_char* grp = w.group();
-                bf16x8 ah[kGroup], al[kGroup];
-#pragma unroll
-                for (int j = 0; j < kGroup; ++j) {
-                    ah[j] = *reinterpret_cast<const lds_bf16x8*>(grp + j * 2048);
-                    al[j] = *reinterpret_cast<const lds_bf16x8*>(grp + j * 2048 + 1024);
-                }
-#pragma unroll
-                for (int j = 0; j < kGroup; ++j) acc[t] = mma_x3(ah[j], al[j], b[j], acc[t]);
-                w.release();
-            }
-        } else {
-            f32x4 b0[kGroup], b1[kGroup];
-#pragma unroll
-            for (int j = 0; j < kGroup; ++j) {
-                b0[j] = *reinterpret_cast<const lds_f32x4*>(bsrc + j * 64);
-                b1[j] = *reinterpret_cast<const lds_f32x4*>(bsrc + j * 64 + 16);
-            }
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                w.acquire();
-                const lds_char* grp = w.group();
-#pragma unroll
-                for (int j = 0; j < kGroup; ++j) {
-                    const f32x4 a0 = *reinterpret_cast<const lds_f32x4*>(grp + j * 2048), a1 = *reinterpret_cast<const lds_f32x4*>(grp + j * 2048 + 1024);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[i], b0[j][i], acc[t], 0, 0, 0);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[i], b1[j][i], acc[t], 0, 0, 0);
-                }
-                w.release();
-            }
+            for (int j = 0; j < kGroup; ++j) acc[t] = Frag<M>::mma(a[j], b[j], acc[t]);
+            w.release();     // (every read of the slot has returned)
         }
     }
     if constexpr (!ROLLED) {      // forward kernel: the epilogues unrolled (measured faster there: 378 vs 365 TFLOP/s on 256 x 8)
@@ -395,15 +377,24 @@ __device__ __forceinline__ void load_x(const float* __restrict__ src, int d_in, 
         }
     }
 }
-// bias of the lane's 16 outputs of a tile (D row of register q: (q&3) + 8 (q>>2) + 4 g) through wave-uniform (scalar)
-// loads: a vector load here would put a compiler-placed vmcnt(0) — a drain of the weight ring — into every tile
+// D tile of a 32 x 32 MFMA: lane = column p (+ half g), register q = row d_row(q, g) — here a feature of the tile that
+// starts at feature `base` (summed in this order: the index arithmetic the compiler hoists keeps its place)
+__device__ __forceinline__ constexpr int d_row(int q, int g = 0, int base = 0) { return base + (q & 3) + 8 * (q >> 2) + 4 * g; }
+// bias of the lane's 16 outputs of a tile through wave-uniform (scalar) loads: a vector load here would put a
+// compiler-placed vmcnt(0) — a drain of the weight ring — into every tile
 __device__ __forceinline__ void load_bias(const float* __restrict__ bt, int g, float* v) {
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-        const int c = (q & 3) + 8 * (q >> 2);
-        const float lo = bt[c], hi = bt[c + 4];
+        const float lo = bt[d_row(q)], hi = bt[d_row(q) + 4];
         v[q] = g ? hi : lo;
     }
+}
+// how both layer epilogues open: v = the accumulators of output tile t + bias
+__device__ __forceinline__ void bias_add(const Args& a, const Layer& L, int t, int g, const f32x16& acc, float* v) {
+    float bias[16];
+    load_bias(a.biases + L.b_off + 32 * t, g, bias);
+#pragma unroll
+    for (int q = 0; q < 16; ++q) v[q] = acc[q] + bias[q];
 }
 
 // The activation code is wave-uniform: ONE branch per tile around sixteen straight-line evaluations — a switch inside
@@ -425,10 +416,10 @@ __device__ __forceinline__ void zero_pad16(float* v, int t, int g, int n_out) {
     if (32 * t + 32 > n_out) {
 #pragma unroll
         for (int q = 0; q < 16; ++q)
-            if (32 * t + (q & 3) + 8 * (q >> 2) + 4 * g >= n_out) v[q] = 0.f;
+            if (d_row(q, g, 32 * t) >= n_out) v[q] = 0.f;
     }
 }
-// 16 floats (register q = feature (q&3) + 8 (q>>2) + 4 g of the tile) -> the lane's row in LDS: four 8- or 16-byte stores
+// 16 floats (register q = feature d_row(q, g) of the tile) -> the lane's row in LDS: four 8- or 16-byte stores
 template <int M>
 __device__ __forceinline__ void store_row16(lds_char* row_tile, int g, const float* v) {
 #pragma unroll
@@ -462,22 +453,19 @@ __device__ __forceinline__ void forward_layer(const Args& a, const Layer& L, boo
     // (more than 8 tiles: the looped epilogue — sixteen unrolled ones beside 256 accumulator registers spill)
     layer_mma<M, NW, NT, (NT > 8)>(w, L.ks_h / kGroup, L.ks_x / kGroup, hrow + g * (P<M>::kStep / 2), xrow + g * (P<M>::kStep / 2),
                               [&](int t, const f32x16& acc) {
-        // D: lane = row p (+ half g), register q = output feature 32 t + (q&3) + 8 (q>>2) + 4 g
-        float bias[16], v[16];
-        load_bias(a.biases + L.b_off + 32 * t, g, bias);
-#pragma unroll
-        for (int q = 0; q < 16; ++q) v[q] = acc[q] + bias[q];
+        float v[16];      // D: lane = row p (+ half g), register q = output feature 32 t + d_row(q, g)
+        bias_add(a, L, t, g, acc, v);
         activate16(v, L.act);
         if (last) {
             if (yrow) {
                 float* dst = yrow + 32 * t + 4 * g;
                 if (32 * t + 32 <= L.n_out) {
 #pragma unroll
-                    for (int q = 0; q < 16; ++q) dst[(q & 3) + 8 * (q >> 2)] = v[q];
+                    for (int q = 0; q < 16; ++q) dst[d_row(q)] = v[q];
                 } else {
 #pragma unroll
                     for (int q = 0; q < 16; ++q)
-                        if (32 * t + (q & 3) + 8 * (q >> 2) + 4 * g < L.n_out) dst[(q & 3) + 8 * (q >> 2)] = v[q];
+                        if (d_row(q, g, 32 * t) < L.n_out) dst[d_row(q)] = v[q];
                 }
             }
         } else {
@@ -596,15 +584,13 @@ __device__ __forceinline__ void recompute_layer(const BwdArgs& ba, int l, Ring<M
     const bool last = l == a.n_layers - 1;
     layer_mma<M, NW, NT, true>(w, L.ks_h / kGroup, L.ks_x / kGroup, hrow + g * (P<M>::kStep / 2), xrow + g * (P<M>::kStep / 2),
                              [&](int t, const f32x16& acc) {
-        float bias[16], v[16];
-        load_bias(a.biases + L.b_off + 32 * t, g, bias);
-#pragma unroll
-        for (int q = 0; q < 16; ++q) v[q] = acc[q] + bias[q];
+        float v[16];
+        bias_add(a, L, t, g, acc, v);
         if (last) {      // dZ = dy * act'(logit); rows past n and features past the width contribute nothing
             float d[16];                     // (every index clamped INTO the row: the last row's pad columns lie past the buffer)
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
-                const int f = 32 * t + 4 * g + (q & 3) + 8 * (q >> 2);
+                const int f = 32 * t + d_row(q, g);
                 d[q] = dyr[f < L.n_out ? f : 0];
             }
             scale_by_act_grad_logit16(d, v, L.act);
@@ -626,15 +612,9 @@ __device__ __forceinline__ void dgrad_layer(const BwdArgs& ba, int l, Ring<M, NW
     layer_mma<M, NW, NT, true>(w, kg_o, 0, hrow + g * (P<M>::kStep / 2), hrow, [&](int mt, const f32x16& acc) {
         // the previous layer's outputs at the lane's 16 features, back from the workspace (same wave, own cache lines)
         float d[16], y[16];
-        if constexpr (P<M>::kF32) {
-            const float* hy = reinterpret_cast<const float*>(wst) + (size_t)(ba.b[l - 1].h_row + 32 * mt + 4 * g) * 32 + p;
+        const auto* hy = reinterpret_cast<const typename P<M>::Elem*>(wst) + (size_t)(ba.b[l - 1].h_row + 32 * mt + 4 * g) * 32 + p;
 #pragma unroll
-            for (int q = 0; q < 16; ++q) y[q] = hy[((q & 3) + 8 * (q >> 2)) * 32];
-        } else {
-            const __bf16* hy = reinterpret_cast<const __bf16*>(wst) + (size_t)(ba.b[l - 1].h_row + 32 * mt + 4 * g) * 32 + p;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) y[q] = (float)hy[((q & 3) + 8 * (q >> 2)) * 32];
-        }
+        for (int q = 0; q < 16; ++q) y[q] = (float)hy[d_row(q) * 32];
 #pragma unroll
         for (int q = 0; q < 16; ++q) d[q] = acc[q];
         scale_by_act_grad_output16(d, y, a.layer[l - 1].act);
@@ -698,7 +678,7 @@ __global__ __launch_bounds__(64 * NW) void mlp_generic_bwd_kernel(BwdArgs ba) {
                         float* dst = ba.dx + (row0 + p) * ba.ld_dx;
 #pragma unroll
                         for (int q = 0; q < 16; ++q) {
-                            const int f = 32 * mt + (q & 3) + 8 * (q >> 2) + 4 * g;
+                            const int f = d_row(q, g, 32 * mt);
                             if (f < a.d_in) dst[f] = dx_written ? dst[f] + acc[q] : acc[q];
                         }
                     }
@@ -725,43 +705,6 @@ __device__ __forceinline__ InTile in_tile(const WgradArgs& a, int l, int it) {
     if (it < mh) return {a.b[l - (l > 0)].h_row + 32 * it, prev - 32 * it, 32 * it};
     return {32 * (it - mh), a.d_in - 32 * (it - mh), prev + 32 * (it - mh)};
 }
-template <int M> struct Frag;
-template <> struct Frag<kBf16> {
-    bf16x8 v;
-    __device__ __forceinline__ void load(const char* p) { v = *reinterpret_cast<const bf16x8*>(p); }
-    __device__ __forceinline__ void ones() {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (__bf16)1.0f;
-    }
-    static __device__ __forceinline__ f32x16 mma(const Frag& a, const Frag& b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v, b.v, c, 0, 0, 0); }
-    static __device__ __forceinline__ f32x16 mma_ones(const Frag& one, const Frag& b, f32x16 c) { return mma(one, b, c); }
-};
-template <> struct Frag<kX3> {      // 8 consecutive fp32 rows of one feature, split in registers (both operands are activations)
-    HiLo v;
-    __device__ __forceinline__ void load(const char* p) { v = split8(*reinterpret_cast<const f32x4*>(p), *reinterpret_cast<const f32x4*>(p + 16)); }
-    __device__ __forceinline__ void ones() {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { v.hi[j] = (__bf16)1.0f; v.lo[j] = (__bf16)0.0f; }
-    }
-    static __device__ __forceinline__ f32x16 mma(const Frag& a, const Frag& b, f32x16 c) { return mma_x3(a.v.hi, a.v.lo, b.v, c); }
-    static __device__ __forceinline__ f32x16 mma_ones(const Frag& one, const Frag& b, f32x16 c) {      // (1 has no lo half)
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(one.v.hi, b.v.lo, c, 0, 0, 0);
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(one.v.hi, b.v.hi, c, 0, 0, 0);
-    }
-};
-template <> struct Frag<kNative> {
-    f32x4 lo, hi;
-    __device__ __forceinline__ void load(const char* p) { lo = *reinterpret_cast<const f32x4*>(p); hi = *reinterpret_cast<const f32x4*>(p + 16); }
-    __device__ __forceinline__ void ones() { lo = hi = f32x4{1.f, 1.f, 1.f, 1.f}; }
-    static __device__ __forceinline__ f32x16 mma(const Frag& a, const Frag& b, f32x16 c) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.lo[i], b.lo[i], c, 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.hi[i], b.hi[i], c, 0, 0, 0);
-        return c;
-    }
-    static __device__ __forceinline__ f32x16 mma_ones(const Frag& one, const Frag& b, f32x16 c) { return mma(one, b, c); }
-};
 template <int M>
 __global__ __launch_bounds__(256) void mlp_generic_wgrad_kernel(WgradArgs a) {
     constexpr int E = P<M>::kElem;
@@ -820,7 +763,7 @@ __global__ __launch_bounds__(256) void mlp_generic_wgrad_kernel(WgradArgs a) {
             }
         }
     }
-    // D: column (lane & 31) = o, row (q&3) + 8 (q>>2) + 4 g = i
+    // D: column (lane & 31) = o, row d_row(q, g) = i
     if (with_bias && g == 0) {      // every row of accb holds the column sums: row 0 = register 0 of lanes 0..31
         float* db = a.partial + (size_t)sp * a.slice + a.b[l].db_off;
         if (64 * op + m < L.n_out) db[64 * op + m] = accb[0][0];
@@ -837,7 +780,7 @@ __global__ __launch_bounds__(256) void mlp_generic_wgrad_kernel(WgradArgs a) {
             if (o >= L.n_out) continue;
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
-                const int i = (q & 3) + 8 * (q >> 2) + 4 * g;
+                const int i = d_row(q, g);
                 if (i < ti[x].n_valid) dst[(size_t)(ti[x].i_base + i) * L.n_out + o] = acc[x][y][q];
             }
         }
@@ -942,125 +885,110 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(EmbedArgs a, const float
 }  // namespace generic
 }  // namespace nfx
 
-// ---- launch: one pair of functions per translation unit = per operand mode (NFX_GENERIC_TU), dispatched by the C entry
-// points of translation unit 0
+// ---- launch: one pair of C functions per translation unit = per operand mode (both on launch_for below), dispatched by the
+// C entry points of unit 0.  (The using-directive reaches the two units that include this file; they hold nothing else.)
 #define NFX_CAT_(a, b) a##b
 #define NFX_CAT(a, b) NFX_CAT_(a, b)
+using namespace nfx::generic;
 namespace {
-template <int M, int NW, bool WIDE = false>
-int launch_fwd(const nfx::generic::Args* args, int grid, int lds, hipStream_t st) {
-    using namespace nfx::generic;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_generic_kernel<M, NW, WIDE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+// the two persistent kernels as one family, picked by the argument structure
+template <int M, int NW, bool WIDE> auto kernel_for(const Args*) { return mlp_generic_kernel<M, NW, WIDE>; }
+template <int M, int NW, bool WIDE> auto kernel_for(const BwdArgs*) { return mlp_generic_bwd_kernel<M, NW, WIDE>; }
+template <int M, int NW, bool WIDE, class A>
+int launch(const A* args, int grid, int lds, hipStream_t st) {
+    const auto kernel = kernel_for<M, NW, WIDE>(args);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((mlp_generic_kernel<M, NW, WIDE>), dim3(grid), dim3(64 * NW), lds, st, *args);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * NW), lds, st, *args);
     return 0;
 }
-template <int M, int NW, bool WIDE = false>
-int launch_bwd(const nfx::generic::BwdArgs* ba, int grid, int lds, hipStream_t st) {
-    using namespace nfx::generic;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_generic_bwd_kernel<M, NW, WIDE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((mlp_generic_bwd_kernel<M, NW, WIDE>), dim3(grid), dim3(64 * NW), lds, st, *ba);
-    return 0;
-}
-bool wide_layers(const nfx::generic::Args& a) {      // a layer of more than 8 output tiles (width > 256)
+bool wide_layers(const Args& a) {      // a layer of more than 8 output tiles (width > 256)
     for (int l = 0; l < a.n_layers; ++l)
         if (a.layer[l].n_tiles > 8) return true;
     return false;
 }
+// which <NW, WIDE> instantiation runs `f`: nw waves around one ring, or one wave with up to 16 accumulator tiles
+template <int M, class A>
+int launch_for(const A* args, const Args& f, int nw, int grid, int lds, hipStream_t st) {
+    if constexpr (M != kBf16) {      // (bf16 keeps a private ring per wave: generic_waves)
+        if (nw == 4) return launch<M, 4, false>(args, grid, lds, st);
+        if (nw == 2) return launch<M, 2, false>(args, grid, lds, st);
+    }
+    if (wide_layers(f)) return launch<M, 1, true>(args, grid, lds, st);
+    return launch<M, 1, false>(args, grid, lds, st);
+}
 }  // namespace
 extern "C" {
-int NFX_CAT(nfx_generic_fwd_m, NFX_GENERIC_TU)(const nfx::generic::Args* args, int nw, int grid, int lds, hipStream_t st) {
-    constexpr int M = NFX_GENERIC_TU;
-#if NFX_GENERIC_TU != 0      // (bf16 keeps a private ring per wave: generic_waves)
-    if (nw == 4) return launch_fwd<M, 4>(args, grid, lds, st);
-    if (nw == 2) return launch_fwd<M, 2>(args, grid, lds, st);
-#endif
-    (void)nw;
-    if (wide_layers(*args)) return launch_fwd<M, 1, true>(args, grid, lds, st);
-    return launch_fwd<M, 1>(args, grid, lds, st);
+int NFX_CAT(nfx_generic_fwd_m, NFX_GENERIC_TU)(const Args* args, int nw, int grid, int lds, hipStream_t st) {
+    return launch_for<NFX_GENERIC_TU>(args, *args, nw, grid, lds, st);
 }
-int NFX_CAT(nfx_generic_bwd_m, NFX_GENERIC_TU)(const nfx::generic::BwdArgs* ba, const nfx::generic::WgradArgs* wa, int nw, int grid, int lds, hipStream_t st) {
-    using namespace nfx::generic;
-    constexpr int M = NFX_GENERIC_TU;
-    int rc;
-#if NFX_GENERIC_TU != 0
-    if (nw == 4) rc = launch_bwd<M, 4>(ba, grid, lds, st);
-    else if (nw == 2) rc = launch_bwd<M, 2>(ba, grid, lds, st);
-    else
-#endif
-        if (wide_layers(ba->f)) rc = launch_bwd<M, 1, true>(ba, grid, lds, st);
-    else rc = launch_bwd<M, 1>(ba, grid, lds, st);
-    (void)nw;
-    if (rc) return rc;
+int NFX_CAT(nfx_generic_bwd_m, NFX_GENERIC_TU)(const BwdArgs* ba, const WgradArgs* wa, int nw, int grid, int lds, hipStream_t st) {
+    if (const int rc = launch_for<NFX_GENERIC_TU>(ba, ba->f, nw, grid, lds, st)) return rc;
     if (wa->dw[0]) {     // (no gradient buffers: the caller wants dLoss/dx only)
         const long long waves = (long long)wa->n_jobs * wa->splits;
         const unsigned wgs = wa->map == 0 ? (unsigned)((waves + 3) / 4)
                                           : (unsigned)((wa->splits + 7) / 8 * ((wa->n_jobs + 3) / 4) * 8);
-        hipLaunchKernelGGL(mlp_generic_wgrad_kernel<M>, dim3(wgs), dim3(256), 0, st, *wa);
+        hipLaunchKernelGGL(mlp_generic_wgrad_kernel<NFX_GENERIC_TU>, dim3(wgs), dim3(256), 0, st, *wa);
     }
     return 0;
 }
 }
 
 #if NFX_GENERIC_TU == 0
-static_assert(nfx::generic::kBf16 == 0 && nfx::generic::kX3 == 1 && nfx::generic::kNative == 2, "NFX_GENERIC_TU = the operand mode");
+static_assert(kBf16 == 0 && kX3 == 1 && kNative == 2, "NFX_GENERIC_TU = the operand mode");
 // waves per workgroup: as many (4, 2, 1) as fit the 160 KiB of LDS beside the shared ring
-static int generic_waves(const nfx::generic::Args& a, long long tiles) {
-    using namespace nfx::generic;
-    const int ring = a.f32 ? P<kNative>::kRingBytes : P<kBf16>::kRingBytes, act = 32 * (a.x_pitch + a.h_pitch);
+static int generic_waves(const Args& a, long long tiles, int ring) {
+    const int act = 32 * (a.x_pitch + a.h_pitch);
     // bf16 keeps a private ring per wave: a group is only 4 MFMAs there, a workgroup barrier per group costs more than the
     // DMA pieces it saves, and the backward's workspace stores sit in the same in-order vmcnt queue the shared ring has to
     // drain to 2 (measured, r05 call K: 256 x 8 forward 380 against 384 TFLOP/s, 128 x 4 backward 126 against 173)
-    if (!a.f32) return 1;
-    for (int l = 0; l < a.n_layers; ++l)
-        if (a.layer[l].n_tiles > 8) return 1;      // (more than 8 output tiles: instantiated for one wave per workgroup only)
+    if (a.mode == kBf16) return 1;
+    if (wide_layers(a)) return 1;      // (more than 8 output tiles: instantiated for one wave per workgroup only)
     int nw = 4;
     while (nw > 1 && (ring + nw * act > 160 * 1024 || tiles < nw)) nw /= 2;
     return nw;
 }
-extern "C" {
-int nfx_launch_mlp_generic(const nfx::generic::Args* args, int max_blocks, hipStream_t st) {
-    using namespace nfx::generic;
-    if (args->n <= 0) return 0;
-    const long long tiles = (args->n + 31) / 32;
-    const int nw = generic_waves(*args, tiles);
+// the launch shape of either persistent kernel: waves per workgroup, workgroups, bytes of LDS
+struct Shape { int nw, grid, lds; };
+static Shape launch_shape(const Args& a, long long tiles, int max_blocks) {
+    const int ring = a.mode == kBf16 ? P<kBf16>::kRingBytes : P<kNative>::kRingBytes;
+    const int nw = generic_waves(a, tiles, ring);
     const long long wgs = (tiles + nw - 1) / nw, cap = max_blocks / nw > 0 ? max_blocks / nw : 1;
-    const int grid = (int)(wgs < cap ? wgs : cap);
-    const int lds = (args->f32 ? P<kNative>::kRingBytes : P<kBf16>::kRingBytes) + nw * 32 * (args->x_pitch + args->h_pitch);
-    if (lds > 160 * 1024) return -lds;      // (the C entry point turns this into NFX_ENOSUP with the numbers)
-    const int rc = args->f32 == kBf16 ? nfx_generic_fwd_m0(args, nw, grid, lds, st)
-                 : args->f32 == kX3 ? nfx_generic_fwd_m1(args, nw, grid, lds, st) : nfx_generic_fwd_m2(args, nw, grid, lds, st);
+    return {nw, (int)(wgs < cap ? wgs : cap), ring + nw * 32 * (a.x_pitch + a.h_pitch)};
+}
+static_assert(P<kX3>::kRingBytes == P<kNative>::kRingBytes, "launch_shape: one ring size for both fp32 data modes");
+extern "C" {
+int nfx_launch_mlp_generic(const Args* args, int max_blocks, hipStream_t st) {
+    if (args->n <= 0) return 0;
+    const Shape s = launch_shape(*args, (args->n + 31) / 32, max_blocks);
+    if (s.lds > 160 * 1024) return -s.lds;      // (the C entry point turns this into NFX_ENOSUP with the numbers)
+    const auto fwd = args->mode == kBf16 ? nfx_generic_fwd_m0 : args->mode == kX3 ? nfx_generic_fwd_m1 : nfx_generic_fwd_m2;
+    const int rc = fwd(args, s.nw, s.grid, s.lds, st);
     return rc ? rc : (int)hipGetLastError();
 }
-int nfx_launch_mlp_generic_bwd(const nfx::generic::BwdArgs* ba, const nfx::generic::WgradArgs* wa, int max_blocks, hipStream_t st) {
-    using namespace nfx::generic;
+int nfx_launch_mlp_generic_bwd(const BwdArgs* ba, const WgradArgs* wa, int max_blocks, hipStream_t st) {
     if (ba->f.n <= 0) return 0;
-    const int nw = generic_waves(ba->f, ba->tiles);
-    const long long wgs = (ba->tiles + nw - 1) / nw, cap = max_blocks / nw > 0 ? max_blocks / nw : 1;
-    const int grid = (int)(wgs < cap ? wgs : cap);
-    const int lds = (ba->f.f32 ? P<kNative>::kRingBytes : P<kBf16>::kRingBytes) + nw * 32 * (ba->f.x_pitch + ba->f.h_pitch);
-    if (lds > 160 * 1024) return -lds;
-    const int rc = ba->f.f32 == kBf16 ? nfx_generic_bwd_m0(ba, wa, nw, grid, lds, st)
-                 : ba->f.f32 == kX3 ? nfx_generic_bwd_m1(ba, wa, nw, grid, lds, st) : nfx_generic_bwd_m2(ba, wa, nw, grid, lds, st);
-    if (rc) return rc;
+    const Shape s = launch_shape(ba->f, ba->tiles, max_blocks);
+    if (s.lds > 160 * 1024) return -s.lds;
+    const auto bwd = ba->f.mode == kBf16 ? nfx_generic_bwd_m0 : ba->f.mode == kX3 ? nfx_generic_bwd_m1 : nfx_generic_bwd_m2;
+    if (const int rc = bwd(ba, wa, s.nw, s.grid, s.lds, st)) return rc;
     if (wa->dw[0]) hipLaunchKernelGGL(mlp_generic_wgrad_reduce_kernel, dim3((unsigned)((wa->slice + 255) / 256)), dim3(256), 0, st, *wa);
     return (int)hipGetLastError();
 }
 int nfx_launch_split_hilo(void* frags, long long n_frags, hipStream_t st) {
     if (n_frags <= 0) return 0;
-    hipLaunchKernelGGL(nfx::generic::split_hilo_kernel, dim3((unsigned)((n_frags * 64 + 255) / 256)), dim3(256), 0, st, static_cast<char*>(frags), n_frags);
+    hipLaunchKernelGGL(split_hilo_kernel, dim3((unsigned)((n_frags * 64 + 255) / 256)), dim3(256), 0, st, static_cast<char*>(frags), n_frags);
     return (int)hipGetLastError();
 }
-int nfx_launch_embed_bwd(const nfx::generic::EmbedArgs* a, const float* d_out, float* dv, hipStream_t st) {
+int nfx_launch_embed_bwd(const EmbedArgs* a, const float* d_out, float* dv, hipStream_t st) {
     if (a->n <= 0) return 0;
-    hipLaunchKernelGGL(nfx::generic::embed_bwd_kernel, dim3((unsigned)((a->n + 255) / 256)), dim3(256), 0, st, *a, d_out, dv);
+    hipLaunchKernelGGL(embed_bwd_kernel, dim3((unsigned)((a->n + 255) / 256)), dim3(256), 0, st, *a, d_out, dv);
     return (int)hipGetLastError();
 }
-int nfx_launch_embed(const nfx::generic::EmbedArgs* a, hipStream_t st) {
+int nfx_launch_embed(const EmbedArgs* a, hipStream_t st) {
     if (a->n <= 0) return 0;
     const long long elems = a->n * ((a->incl_input ? 3 : 0) + 6 * a->n_freqs);
-    hipLaunchKernelGGL(nfx::generic::embed_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, *a);
+    hipLaunchKernelGGL(embed_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, *a);
     return (int)hipGetLastError();
 }
 }

@@ -35,7 +35,8 @@ struct Args {
     int ld_y, col0;
     int n_layers;
     int x_pitch, h_pitch;   // LDS row pitches in bytes: (features padded to 64) x element size + 16 of the input / the widest layer
-    int f32;                // operands: 0 bf16 (1-KiB fragments), 1 fp32 (2-KiB fragments, v_mfma_f32_32x32x2_f32)
+    int mode;               // operand mode = the C-ABI's NFX_PREC_*: 0 bf16 (1-KiB fragments), 1 fp32-class (2-KiB fragments of bf16 hi / lo
+                            // planes, fp32 activations), 2 native fp32 (2-KiB fragments, v_mfma_f32_32x32x2_f32)
     Layer layer[kMaxLayers];
 };
 // Embedder (embedder.py:23-47): out[:, col0 ...] = [x, sin(f_0 x), cos(f_0 x), sin(f_1 x), cos(f_1 x), ...], f_k = 2^k,

@@ -11,7 +11,9 @@ that must not change a single bit.  One process per library:
   tests/bwd_probes.py.
 --group bwd: the training backward kernels behind bwd_tile.hpp and mlp128_bwd_ring.hpp (mlp128_bwd.hip, mlp128_bwd_fused.hip,
   nerf_bwd.hip) on the launch shapes of tests/bwd_probes.py, with dense seeded upstream gradients of which about 40 % of the
-  rows are exact zeros, under every path and option that selects another kernel."""
+  rows are exact zeros, under every path and option that selects another kernel.
+--group generic (also with --pack-only): the runtime-shaped MLP (mlp_generic.hip, capi_generic.cpp) in its three operand modes:
+  the packers' bytes for every shape of tests/generic_exact_cases.py, and forward, dW, db, dx of four of them at 97 and 161 rows."""
 import hashlib
 import os
 import sys
@@ -31,8 +33,8 @@ from tests import common, nerf_point_cases as pc  # noqa: E402
 mode = sys.argv[1]
 pack_only = '--pack-only' in sys.argv
 group = sys.argv[sys.argv.index('--group') + 1] if '--group' in sys.argv else 'geom'
-assert group in ('geom', 'rows', 'bwd') and not (pack_only and group != 'geom')
-path = os.path.join(ROOT, 'build', 'geom_identity_pack.pt' if pack_only else 'geom_identity.pt' if group == 'geom' else 'geom_identity_%s.pt' % group)     # build/ is not tracked
+assert group in ('geom', 'rows', 'bwd', 'generic') and not (pack_only and group not in ('geom', 'generic'))
+path = os.path.join(ROOT, 'build', 'geom_identity%s%s.pt' % ('' if group == 'geom' else '_' + group, '_pack' if pack_only else ''))     # build/ is not tracked
 out = {}
 
 
@@ -203,7 +205,51 @@ def bwd_cases():
     torch.cuda.synchronize()
 
 
-{'geom': geom_cases, 'rows': rows_cases, 'bwd': bwd_cases}[group]()
+def generic_cases():
+    """The runtime-shaped MLP (mlp_generic.hip, capi_generic.cpp) in its three operand modes.  The packers' bytes (forward and
+    train blob) for every shape of tests/generic_exact_cases.py; on the GPU forward, dW, db and dx, with and without want_dx, of
+    four of them on real-valued seeded data (Glorot weights, non-zero biases: no sum is exact by construction), with a sigmoid
+    and a softplus output and a sigmoid hidden layer, at 97 rows (four waves per workgroup: one workgroup whose fourth wave has
+    a partial tile) and 161 (a second workgroup, two of whose waves have no tile)."""
+    from tests import generic_exact_cases as G
+
+    def glorot(name, acts=None):
+        c = G.case(name)
+        rng = np.random.default_rng(900 + sorted(G.SHAPES).index(name))
+        ks = [rng.uniform(-1, 1, size=k.shape).astype(np.float32) * np.float32(np.sqrt(6. / sum(k.shape))) for k, _ in c.layers]
+        bs = [rng.normal(size=b.shape).astype(np.float32) * np.float32(.1) for _, b in c.layers]
+        return c, rng, ks, bs, acts or c.acts
+
+    for name in sorted(G.SHAPES):
+        c, _, ks, bs, acts = glorot(name)
+        for prec in G.PRECS:
+            for train in (False, True):
+                out['pack%s/%s %s' % ('_train' if train else '', name, prec)] = ops.GenericNet(ks, bs, acts, c.skip_at or None, train=train, prec=prec).blob
+    if pack_only:
+        return
+    dev = torch.device('cuda:0')
+    for name, acts in (('w128x3_skip1', ['relu'] * 3 + ['sigmoid']), ('two_skips', ['relu', 'relu', 'softplus']),
+                       ('in283', ['sigmoid', None]), ('wide320', None)):
+        c, rng, ks, bs, acts = glorot(name, acts)
+        x_all = rng.normal(size=(161, c.d_in)).astype(np.float32)
+        dy_all = rng.normal(size=(161, c.widths[-1])).astype(np.float32)
+        for prec in G.PRECS:
+            net = ops.GenericNet(ks, bs, acts, c.skip_at or None, train=True, prec=prec).to(dev)
+            for n in (97, 161):
+                x, dy = torch.from_numpy(x_all[:n]).to(dev), torch.from_numpy(dy_all[:n]).to(dev)
+                key = 'generic/%s %s n %d ' % (name, prec, n)
+                out[key + 'y'] = ops.mlp_generic_fwd(x, net)
+                for want_dx in (False, True):
+                    flat = [torch.full(k.shape, .5, device=dev) for k in ks] + [torch.full(b.shape, -.25, device=dev) for b in bs]      # (the kernels ADD)
+                    dx = ops.mlp_generic_bwd(x, net, dy, flat[:len(ks)], flat[len(ks):], want_dx=want_dx)
+                    out[key + 'dW db want_dx %d' % want_dx] = torch.cat([t.reshape(-1) for t in flat])
+                    if want_dx:
+                        out[key + 'dx'] = dx
+                out[key + 'dx alone'] = ops.mlp_generic_bwd(x, net, dy, None, None, want_dx=True)
+    torch.cuda.synchronize()
+
+
+{'geom': geom_cases, 'rows': rows_cases, 'bwd': bwd_cases, 'generic': generic_cases}[group]()
 
 out = {k: v.detach().cpu().contiguous() for k, v in out.items()}
 lib = os.environ.get('NFX_LIB_PATH', 'the tree\'s libnfx.so')

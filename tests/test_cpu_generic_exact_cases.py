@@ -122,11 +122,15 @@ def test_the_cases_cover_the_code_paths():
 def test_restated_host_decisions_match_the_source():
     hip = open(os.path.join(ROOT, 'nerfactor_amd', 'csrc', 'mlp_generic.hip')).read()
     cpp = open(os.path.join(ROOT, 'nerfactor_amd', 'csrc', 'capi_generic.cpp')).read()
-    for text in ('static constexpr int kRingGroups = 3;', 'static constexpr int kFrag = 32 * 16 * kElem;', 'if (!a.f32) return 1;',
-                 'if (a.layer[l].n_tiles > 8) return 1;', 'int nw = 4;',
+    for text in ('static constexpr int kRingGroups = 3;', 'static constexpr int kFrag = 32 * 16 * kElem;', 'if (a.mode == kBf16) return 1;',
+                 'if (wide_layers(a)) return 1;', 'if (a.layer[l].n_tiles > 8) return true;', 'int nw = 4;',
                  'while (nw > 1 && (ring + nw * act > 160 * 1024 || tiles < nw)) nw /= 2;',
-                 'act = 32 * (a.x_pitch + a.h_pitch);', 'if (wide_layers(*args)) return launch_fwd<M, 1, true>(args, grid, lds, st);',
-                 'if (wide_layers(ba->f)) rc = launch_bwd<M, 1, true>(ba, grid, lds, st);',
+                 'act = 32 * (a.x_pitch + a.h_pitch);', 'const int ring = a.mode == kBf16 ? P<kBf16>::kRingBytes : P<kNative>::kRingBytes;',
+                 # one dispatch for the forward and the backward kernel: NW = 4 | 2 in the fp32 modes only, else WIDE or not
+                 'if constexpr (M != kBf16) {', 'if (nw == 4) return launch<M, 4, false>(args, grid, lds, st);',
+                 'if (nw == 2) return launch<M, 2, false>(args, grid, lds, st);',
+                 'if (wide_layers(f)) return launch<M, 1, true>(args, grid, lds, st);', 'return launch<M, 1, false>(args, grid, lds, st);',
+                 'return launch_for<NFX_GENERIC_TU>(args, *args, nw, grid, lds, st);', 'launch_for<NFX_GENERIC_TU>(ba, ba->f, nw, grid, lds, st)',
                  'const long long t0 = a.tiles * sp / a.splits, t1 = a.tiles * (sp + 1) / a.splits;',
                  'const long long wgs = (tiles + nw - 1) / nw, cap = max_blocks / nw > 0 ? max_blocks / nw : 1;'):
         assert text in hip, text
