@@ -343,6 +343,51 @@ NFX_API int nfx_mesh_lvis(const void *dev_blob, size_t blob_bytes, const void *h
                           const float *dev_normal, const float *dev_alpha, int64_t n, const float *dev_lxyz,
                           int n_lights, float eps, float *dev_lvis, void *stream);
 
+/* Iso-surface of a scalar lattice by marching tetrahedra (csrc/isosurface.hip): indexed triangles,
+ * every vertex once, closed wherever the surface does not meet the lattice's boundary.
+ *   Lattice   dev_field: float32 [nx, ny, nz], z fastest, every n >= 2, nx ny nz < NFX_ISOSURFACE_MAX_POINTS; point
+ *             (a, b, c) has flat index (a ny + b) nz + c and sits at origin[k] + idx[k] * spacing[k] (fp32, multiply then
+ *             add; origin, spacing: 3 host floats each, finite, spacing > 0).  A point is inside when field > iso,
+ *             strictly; a NaN is outside.
+ *   Split     cell (i, j, k) — the cube between point (i, j, k) and (i + 1, j + 1, k + 1), flat index that of its lowest
+ *             point — is cut into six tetrahedra around its main diagonal (Kuhn): for the permutation (p0, p1, p2) of the
+ *             axes, in lexicographic order tet 0..5, c0 = (0,0,0), c1 = c0 + e_p0, c2 = c1 + e_p1, c3 = (1,1,1).
+ *   Vertices  a lattice point owns the edges to itself + (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1), classes
+ *             0..6, where that end exists.  An edge whose ends differ in inside-ness carries one vertex,
+ *             t = (iso - f_P) / (f_Q - f_P), v = P + t * (Q - P) per component (P the owner, Q the other end, both placed by
+ *             the rule above; fp32, IEEE division, nothing fused).  Vertex order: ascending (owner's flat index, class).
+ *   Triangles per tet and 4-bit inside mask (bit n = corner c_n): 0 or 4 inside: none; 1 or 3: one triangle on the three
+ *             edges at the lone corner, towards the other corners in ascending order; 2 inside (i < j), 2 outside (k < l):
+ *             the quad q = (i,k) (i,l) (j,l) (j,k) as (q0, q1, q2) and (q0, q2, q3).  Winding: (v1 - v0) x (v2 - v0) points
+ *             from the inside corners to the outside corners — decided per triangle with every crossing at its edge's
+ *             midpoint on the unit cube, by exchanging the last two vertices where needed.  Triangle order: ascending
+ *             (cell's flat index, tet, triangle).  A corner exactly at iso is outside; the zero-area triangles this can
+ *             give are kept.
+ *   nfx_isosurface_tables           PURE HOST.  tri_table: int8 [6][16][2][3][2] — tet, mask, triangle, vertex, the two
+ *                                   corners (a < b) of the vertex's edge, -1 where there is no triangle; edge_table: int8
+ *                                   [6][4][4][4] — tet, corner a, corner b, (class, owner's offset x, y, z) for a < b,
+ *                                   -1 elsewhere.
+ *   nfx_isosurface_workspace_bytes  0 for a lattice outside the limits.  The workspace (16-byte aligned) as int32 words,
+ *                                   B = ceil(n / 1024), pad4(x) = x rounded up to 4: [nv, nf, overflow, 0][pad4(B) vertex
+ *                                   block offsets][pad4(B) triangle block offsets][pad4(n) per-point vertex offsets]
+ *                                   [pad4(n) per-cell triangle offsets], then bytes [pad4(n) crossing masks, bit = class]
+ *                                   [pad4(n) triangle counts].
+ *   nfx_isosurface_count            fills the workspace: the counts, their exclusive scans (four launches, the
+ *                                   library's ascending block scan, no host sync, no atomics) and the totals nv, nf in
+ *                                   words 0 and 1.  Word 2 is non-zero when a count passed 2^31 - 1: the totals are then
+ *                                   meaningless and emit must not be called.
+ *   nfx_isosurface_emit             dev_vertices float32 [nv, 3], dev_faces int32 [nf, 3] with nv, nf the totals read back
+ *                                   by the caller (0 <= nv < 2^31, 3 nf < 2^31); writes every element, reads nothing of the
+ *                                   outputs; never stores outside the nv and nf rows it was given.  One launch.         */
+#define NFX_ISOSURFACE_MAX_POINTS (1ll << 31)
+NFX_API int nfx_isosurface_tables(int8_t *tri_table, int8_t *edge_table);
+NFX_API size_t nfx_isosurface_workspace_bytes(int nx, int ny, int nz);
+NFX_API int nfx_isosurface_count(const float *dev_field, int nx, int ny, int nz, float iso, void *dev_workspace,
+                                 size_t workspace_bytes, void *stream);
+NFX_API int nfx_isosurface_emit(const float *dev_field, int nx, int ny, int nz, float iso, const float *origin,
+                                const float *spacing, const void *dev_workspace, size_t workspace_bytes, int64_t nv,
+                                int64_t nf, float *dev_vertices, int32_t *dev_faces, void *stream);
+
 /* Rusinkiewicz coordinates (phi_d, theta_h, theta_d), util/geom.py:152-192. a,b [n,3]. */
 NFX_API int nfx_dir2rusink(const float *dev_a, const float *dev_b, int64_t n, float *dev_rusink,
                    void *stream);

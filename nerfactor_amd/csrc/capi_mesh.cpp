@@ -1,5 +1,7 @@
-// capi_mesh.cpp — C-ABI entry points of the mesh BVH builder (mesh_bvh.cpp, host only) and the ray casts (mesh_cast.hip).
+// capi_mesh.cpp — C-ABI entry points of the mesh BVH builder (mesh_bvh.cpp, host only), the ray casts (mesh_cast.hip) and the
+// iso-surface extraction (isosurface.hip).
 #include <hip/hip_runtime.h>
+#include <math.h>
 
 #include "capi_common.hpp"
 #include "mesh_bvh.hpp"
@@ -14,6 +16,14 @@ int checked_counts(const char* who, const void* blob, size_t blob_bytes, const v
     if (nfx::mesh::check_header(h, blob_bytes, msg, sizeof msg)) return nfx_fail(NFX_EINVAL, "%s: %s", who, msg);
     *n_nodes = h->n_nodes;
     *n_tris = h->n_tris;
+    return NFX_OK;
+}
+
+// the lattice's point count, or a recorded failure
+int checked_lattice(const char* who, int nx, int ny, int nz, long long* n) {
+    REQUIRE(nx >= 2 && ny >= 2 && nz >= 2, "%s: a %d x %d x %d lattice (at least 2 points per axis)", who, nx, ny, nz);
+    *n = (long long)nx * ny * nz;
+    REQUIRE(*n < NFX_ISOSURFACE_MAX_POINTS, "%s: %d x %d x %d = %lld lattice points (fewer than 2^31)", who, nx, ny, nz, *n);
     return NFX_OK;
 }
 }  // namespace
@@ -48,5 +58,51 @@ int nfx_mesh_lvis(const void* blob, size_t blob_bytes, const void* host_header, 
     REQUIRE(xyz && normal && alpha && lxyz && lvis, "nfx_mesh_lvis: null pointer");
     return nfx_hip_result(nfx_launch_mesh_lvis(blob, n_nodes, n_tris, xyz, normal, alpha, n, lxyz, n_lights, eps, lvis, (hipStream_t)stream),
                           "mesh_lvis");
+}
+
+int nfx_isosurface_tables(int8_t* tri_table, int8_t* edge_table) {
+    REQUIRE(tri_table && edge_table, "nfx_isosurface_tables: null pointer");
+    nfx_isosurface_host_tables(tri_table, edge_table);
+    return NFX_OK;
+}
+
+size_t nfx_isosurface_workspace_bytes(int nx, int ny, int nz) {
+    if (nx < 2 || ny < 2 || nz < 2 || (long long)nx * ny * nz >= NFX_ISOSURFACE_MAX_POINTS) return 0;
+    return nfx_isosurface_ws_bytes((long long)nx * ny * nz);
+}
+
+int nfx_isosurface_count(const float* field, int nx, int ny, int nz, float iso, void* workspace, size_t workspace_bytes, void* stream) {
+    long long n;
+    if (int rc = checked_lattice("nfx_isosurface_count", nx, ny, nz, &n)) return rc;
+    REQUIRE(!isnan(iso), "nfx_isosurface_count: iso is NaN");
+    REQUIRE(field && workspace, "nfx_isosurface_count: null pointer");
+    REQUIRE(workspace_bytes >= nfx_isosurface_ws_bytes(n), "nfx_isosurface_count: workspace of %zu bytes, %zu needed", workspace_bytes,
+            nfx_isosurface_ws_bytes(n));
+    if (!ALIGNED(workspace, 16)) return nfx_fail(NFX_EALIGN, "nfx_isosurface_count: workspace must be 16-byte aligned");
+    return nfx_hip_result(nfx_launch_isosurface_count(field, nx, ny, nz, iso, workspace, (hipStream_t)stream), "isosurface_count");
+}
+
+int nfx_isosurface_emit(const float* field, int nx, int ny, int nz, float iso, const float* origin, const float* spacing,
+                        const void* workspace, size_t workspace_bytes, int64_t nv, int64_t nf, float* vertices, int32_t* faces, void* stream) {
+    long long n;
+    if (int rc = checked_lattice("nfx_isosurface_emit", nx, ny, nz, &n)) return rc;
+    REQUIRE(!isnan(iso), "nfx_isosurface_emit: iso is NaN");
+    REQUIRE(origin && spacing, "nfx_isosurface_emit: null origin or spacing");
+    for (int k = 0; k < 3; ++k) {
+        REQUIRE(isfinite(origin[k]), "nfx_isosurface_emit: origin[%d] = %g is not finite", k, origin[k]);
+        REQUIRE(isfinite(spacing[k]) && spacing[k] > 0.f, "nfx_isosurface_emit: spacing[%d] = %g (finite, > 0)", k, spacing[k]);
+    }
+    REQUIRE(nv >= 0 && nv < (1ll << 31), "nfx_isosurface_emit: nv = %lld vertices (0 .. 2^31 - 1)", (long long)nv);
+    REQUIRE(nf >= 0 && 3 * nf < (1ll << 31), "nfx_isosurface_emit: nf = %lld triangles, 3 nf = %lld (below 2^31)", (long long)nf,
+            (long long)(3 * nf));
+    REQUIRE(field && workspace, "nfx_isosurface_emit: null pointer");
+    REQUIRE(workspace_bytes >= nfx_isosurface_ws_bytes(n), "nfx_isosurface_emit: workspace of %zu bytes, %zu needed", workspace_bytes,
+            nfx_isosurface_ws_bytes(n));
+    if (!ALIGNED(workspace, 16)) return nfx_fail(NFX_EALIGN, "nfx_isosurface_emit: workspace must be 16-byte aligned");
+    if (nv == 0 && nf == 0) return NFX_OK;
+    REQUIRE((nv == 0 || vertices) && (nf == 0 || faces), "nfx_isosurface_emit: null output");
+    return nfx_hip_result(nfx_launch_isosurface_emit(field, nx, ny, nz, iso, origin, spacing, workspace, (int)nv, (int)nf, vertices, faces,
+                                                     (hipStream_t)stream),
+                          "isosurface_emit");
 }
 }

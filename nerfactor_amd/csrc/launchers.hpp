@@ -47,6 +47,12 @@ int nfx_launch_mesh_cast(const void* blob, int n_nodes, int n_tris, const float*
                          hipStream_t st);
 int nfx_launch_mesh_lvis(const void* blob, int n_nodes, int n_tris, const float* xyz, const float* normal, const float* alpha, long long n,
                          const float* lxyz, int n_lights, float eps, float* lvis, hipStream_t st);
+// ---- isosurface.hip (workspace layout and tables: include/nfx.h)
+size_t nfx_isosurface_ws_bytes(long long n_pts);
+void nfx_isosurface_host_tables(int8_t* tri, int8_t* edge);
+int nfx_launch_isosurface_count(const float* field, int nx, int ny, int nz, float iso, void* ws, hipStream_t st);
+int nfx_launch_isosurface_emit(const float* field, int nx, int ny, int nz, float iso, const float* origin, const float* spacing,
+                               const void* ws, int nv, int nf, float* vertices, int* faces, hipStream_t st);
 // ---- loss.hip
 int nfx_launch_pair_loss(int bwd, const nfx_loss_term* terms, int n_terms, const float* alpha, float bg, long long n, float* loss,
                          const float* dloss, hipStream_t st);

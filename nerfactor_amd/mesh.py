@@ -79,13 +79,21 @@ def read_ply(path):
     return vertices, faces.astype(np.int32)
 
 
-def write_ply(path, vertices, faces, binary=True):
-    """The triangle mesh as a PLY file with float x, y, z and `list uchar int vertex_indices` faces."""
+def write_ply(path, vertices, faces, binary=True, normals=None):
+    """The triangle mesh as a PLY file with float x, y, z and `list uchar int vertex_indices` faces; with `normals` [nv, 3]
+    also float nx, ny, nz per vertex."""
     v = np.asarray(vertices, dtype='<f4').reshape(-1, 3)
     f = np.asarray(faces, dtype='<i4').reshape(-1, 3)
-    head = ("ply\nformat %s 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+    props = "property float x\nproperty float y\nproperty float z\n"
+    if normals is not None:
+        n = np.asarray(normals, dtype='<f4').reshape(-1, 3)
+        if n.shape != v.shape:
+            raise ValueError("write_ply: %d normals for %d vertices" % (n.shape[0], v.shape[0]))
+        v = np.ascontiguousarray(np.concatenate((v, n), 1))
+        props += "property float nx\nproperty float ny\nproperty float nz\n"
+    head = ("ply\nformat %s 1.0\nelement vertex %d\n%s"
             "element face %d\nproperty list uchar int vertex_indices\nend_header\n"
-            % ('binary_little_endian' if binary else 'ascii', v.shape[0], f.shape[0]))
+            % ('binary_little_endian' if binary else 'ascii', v.shape[0], props, f.shape[0]))
     with open(path, 'wb') as h:
         h.write(head.encode('ascii'))
         if binary:
@@ -95,7 +103,7 @@ def write_ply(path, vertices, faces, binary=True):
             h.write(rec.tobytes())
         else:
             for row in v:
-                h.write(('%r %r %r\n' % tuple(float(x) for x in row)).encode('ascii'))
+                h.write((' '.join('%r' % float(x) for x in row) + '\n').encode('ascii'))
             for row in f:
                 h.write(('3 %d %d %d\n' % tuple(int(x) for x in row)).encode('ascii'))
 

@@ -854,6 +854,105 @@ def mesh_lvis(blob, header, xyz, normal, alpha, lxyz, eps, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------ iso-surface
+ISOSURFACE_MAX_POINTS = 1 << 31     # nfx.h: NFX_ISOSURFACE_MAX_POINTS
+
+
+def isosurface_tables():
+    """(tri int8 [6, 16, 2, 3, 2], edge int8 [6, 4, 4, 4]): the marching-tetrahedra tables of the kernels
+    (nfx_isosurface_tables; layout in include/nfx.h).  Pure host code, no GPU needed."""
+    tri, edge = np.zeros((6, 16, 2, 3, 2), dtype=np.int8), np.zeros((6, 4, 4, 4), dtype=np.int8)
+    check(lib.nfx_isosurface_tables(tri.ctypes.data, edge.ctypes.data), 'nfx_isosurface_tables')
+    return tri, edge
+
+
+def _iso_field(field):
+    if not isinstance(field, torch.Tensor) or not field.is_cuda:
+        raise _capi.NfxError("isosurface: field must be a CUDA/ROCm tensor (libnfx has no CPU path)")
+    if field.dtype != torch.float32:
+        raise _capi.NfxError("isosurface: field must be float32, got %s" % field.dtype)
+    if field.dim() != 3:
+        raise _capi.NfxError("isosurface: field has shape %s, expected [nx, ny, nz]" % (tuple(field.shape),))
+    if not field.is_contiguous():
+        raise _capi.NfxError("isosurface: field must be contiguous (z fastest), strides %s of shape %s"
+                             % (tuple(field.stride()), tuple(field.shape)))
+    nx, ny, nz = (int(s) for s in field.shape)
+    if min(nx, ny, nz) < 2:
+        raise _capi.NfxError("isosurface: a %d x %d x %d lattice (at least 2 points per axis)" % (nx, ny, nz))
+    if nx * ny * nz >= ISOSURFACE_MAX_POINTS:
+        raise _capi.NfxError("isosurface: %d x %d x %d = %d lattice points (fewer than 2^31)" % (nx, ny, nz, nx * ny * nz))
+    return nx, ny, nz
+
+
+def _iso_workspace(ws, shape, device):
+    nbytes = lib.nfx_isosurface_workspace_bytes(*shape)
+    if ws is None:
+        return torch.empty((nbytes // 4,), dtype=torch.int32, device=device)
+    if not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.dtype == torch.int32 and ws.is_contiguous() and ws.numel() * 4 >= nbytes):
+        raise _capi.NfxError("isosurface: the workspace must be a contiguous CUDA int32 tensor of at least %d words" % (nbytes // 4))
+    return ws
+
+
+def isosurface_workspace(shape, device):
+    """The int32 workspace of isosurface_count / isosurface_emit for a lattice of `shape` = (nx, ny, nz)."""
+    return _iso_workspace(None, tuple(int(s) for s in shape), device)
+
+
+def isosurface_count(field, iso, ws=None):
+    """The workspace of a lattice, filled (nfx_isosurface_count; no host sync): ws[0] = vertices, ws[1] = triangles,
+    ws[2] != 0 when a count does not fit int32."""
+    shape = _iso_field(field)
+    ws = _iso_workspace(ws, shape, field.device)
+    check(lib.nfx_isosurface_count(_ptr(field), *shape, float(iso), _ptr(ws), ws.numel() * 4, _stream()), 'nfx_isosurface_count')
+    return ws
+
+
+def isosurface_emit(field, iso, origin, spacing, ws, nv, nf, vertices=None, faces=None):
+    """(vertices[nv, 3] float32, faces[nf, 3] int32) from a counted workspace and its two totals (nfx_isosurface_emit)."""
+    shape = _iso_field(field)
+    ws = _iso_workspace(ws, shape, field.device)
+    origin, spacing = [float(x) for x in origin], [float(x) for x in spacing]
+    if len(origin) != 3 or len(spacing) != 3:
+        raise _capi.NfxError("isosurface: origin and spacing are three numbers each")
+    if not all(s > 0 and np.isfinite(s) for s in spacing):
+        raise _capi.NfxError("isosurface: spacing = %s (finite, > 0 on every axis)" % (spacing,))
+    if nv >= 2 ** 31 or 3 * nf >= 2 ** 31:
+        raise _capi.NfxError("isosurface: nv = %d vertices, nf = %d triangles (nv < 2^31 and 3 nf = %d < 2^31)" % (nv, nf, 3 * nf))
+    if vertices is None:
+        vertices = torch.empty((nv, 3), dtype=torch.float32, device=field.device)
+    if faces is None:
+        faces = torch.empty((nf, 3), dtype=torch.int32, device=field.device)
+    for t, name, dt, n in ((vertices, 'vertices', torch.float32, nv), (faces, 'faces', torch.int32, nf)):
+        if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == (n, 3)):
+            raise _capi.NfxError("isosurface: `%s` must be a contiguous CUDA %s [%d, 3] tensor" % (name, dt, n))
+    check(lib.nfx_isosurface_emit(_ptr(field), *shape, float(iso), (ctypes.c_float * 3)(*origin), (ctypes.c_float * 3)(*spacing),
+                                  _ptr(ws), ws.numel() * 4, int(nv), int(nf), _ptr(vertices), _ptr(faces), _stream()),
+          'nfx_isosurface_emit')
+    return vertices, faces
+
+
+def isosurface(field, iso, origin=(0., 0., 0.), spacing=(1., 1., 1.)):
+    """(vertices[nv, 3] float32, faces[nf, 3] int32) on the device: the surface field = iso of float32 field[nx, ny, nz] by
+    marching tetrahedra (include/nfx.h), inside where field > iso, normals pointing out of the inside; lattice point (a, b, c)
+    sits at origin + (a, b, c) * spacing.  An empty surface gives shapes (0, 3).  One host read: the two totals, between the
+    counting and the writing pass."""
+    _iso_field(field)
+    spacing = [float(x) for x in spacing]
+    if len(spacing) != 3 or not all(s > 0 and np.isfinite(s) for s in spacing):
+        raise _capi.NfxError("isosurface: spacing = %s (three numbers, finite, > 0 on every axis)" % (spacing,))
+    if not np.isfinite(float(iso)):
+        raise _capi.NfxError("isosurface: iso = %r is not finite" % (iso,))
+    finite = all_finite(field)
+    ws = isosurface_count(field, iso)
+    nv, nf, overflow, bad = (int(x) for x in torch.cat((ws[:3], (~finite).to(torch.int32).reshape(1))).tolist())
+    if bad:
+        raise _capi.NfxError("isosurface: the %s field holds Inf or NaN" % (tuple(field.shape),))
+    if overflow:
+        raise _capi.NfxError("isosurface: the vertex or triangle count of this %s lattice passes 2^31 - 1 (nv < 2^31, 3 nf < 2^31)"
+                             % (tuple(field.shape),))
+    return isosurface_emit(field, iso, origin, spacing, ws, nv, nf)
+
+
 def _shade_common(xyz, cam, normal, albedo, rough, spec, lvis, lxyz, lareas, lvis_row=None):
     xyz = _dev(xyz, 'xyz', (None, 3))
     n = xyz.shape[0]
