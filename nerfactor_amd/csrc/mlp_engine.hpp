@@ -297,7 +297,15 @@ __device__ __forceinline__ void layer_pre(WStream& ws, int tid, const float* __r
 //     q = 3L      : half 0 -> x[0],                 half 1 -> x[2]
 //     q = 3L + 1  : half 0 -> x[1],                 half 1 -> 0
 //     else        : 0
-// so the two halves split the 6L+3 features with no duplicated transcendental work.
+// so the two halves split the 6L+3 features between them.
+// What is and is not duplicated.  posenc() below is the per-LANE form: lane (h, p) fills the slots of half h for the point it
+// was handed.  With L <= 4 (v_sin_f32 / v_cos_f32, one instruction per slot) a lane computes only its own half's functions:
+// nothing is done twice.  With L > 4 the angle-doubling chain needs BOTH sn and cs of every band, so the lane of half 0 and
+// the lane of half 1 of the same point run the identical sincos_cw + doubling chain and each keeps one of the two results:
+// every sine and cosine is computed twice per point.  posenc_sets() + exchange_sets() are the per-POINT form for kernels
+// whose lanes p and p + 32 hold a point of column tile 0 and one of column tile 1 (nerf_mlp_v6.hip): each lane encodes ONE
+// point, keeps the set of its own half and trades the other set with lane p ^ 32 — every function once per point, the
+// same operations in the same order, so the same bits.
 // --------------------------------------------------------------------------------------
 template <int L>
 struct PeSlots {
@@ -338,6 +346,99 @@ __device__ __forceinline__ void posenc(const float (&x)[3], int h, int c,
     for (int s = 0; s < PeSlots<L>::kKS; ++s) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) out[s][c][j] = (__bf16)v[8 * s + j];
+    }
+}
+
+// BOTH slot sets of one point: s0 = what posenc(x, 0, ..) writes (sines, x[0], x[1]), s1 = what posenc(x, 1, ..) writes
+// (cosines, x[2], 0).  The operations and their order are posenc's, each done once.
+template <int L>
+__device__ __forceinline__ void posenc_sets(const float (&x)[3], bf16x8 (&s0)[PeSlots<L>::kKS],
+                                            bf16x8 (&s1)[PeSlots<L>::kKS]) {
+    constexpr int NQ = PeSlots<L>::kKS * 8;
+    float v0[NQ], v1[NQ];
+#pragma unroll
+    for (int q = 3 * L; q < NQ; ++q) {
+        v0[q] = q == 3 * L ? x[0] : q == 3 * L + 1 ? x[1] : 0.0f;
+        v1[q] = q == 3 * L ? x[2] : 0.0f;
+    }
+    if constexpr (L <= 4) {
+#pragma unroll
+        for (int q = 0; q < 3 * L; ++q) {
+            const float arg = x[q % 3] * (float)(1 << (q / 3));
+            v0[q] = sin_shifted_small(arg, 0);
+            v1[q] = sin_shifted_small(arg, 1);
+        }
+    } else {
+#pragma unroll
+        for (int d = 0; d < 3; ++d)
+#pragma unroll
+            for (int k0 = 0; k0 < L; k0 += 5) {
+                float sn, cs;
+                sincos_cw(x[d] * (float)(1 << k0), sn, cs);
+#pragma unroll
+                for (int k = k0; k < k0 + 5 && k < L; ++k) {
+                    v0[3 * k + d] = sn;
+                    v1[3 * k + d] = cs;
+                    const float s2 = 2.0f * sn * cs;
+                    cs = fmaf(-2.0f * sn, sn, 1.0f);
+                    sn = s2;
+                }
+            }
+    }
+#pragma unroll
+    for (int s = 0; s < PeSlots<L>::kKS; ++s) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            s0[s][j] = (__bf16)v0[8 * s + j];
+            s1[s][j] = (__bf16)v1[8 * s + j];
+        }
+    }
+}
+
+// Lane (h, p) holds the two sets of the point of column tile h.  Slot set h of column tile c belongs into out[s][c] of the
+// lanes of half h: the lane keeps the set of its own half (out[s][h] = its set h), sends its set 1 - h to lane p ^ 32, the
+// lane of half 1 - h at the same column, and receives that lane's set h, which is the other column tile's
+// (out[s][1 - h]).  Through ds_bpermute (the LDS crossbar, no LDS allocation, counted
+// by lgkmcnt), not v_permlane32_swap: lvis_v2.hip's header.  `partner` = ((lane ^ 32) << 2), the byte address of the source lane.
+// The two encoders' sets go in ONE batch: every dword to send is picked first, then all ds_bpermute are issued back to back and
+// their results are taken with counted lgkmcnt waits.  The scheduling fences keep the batch together: left alone, the
+// scheduler interleaves pick / permute / select per dword to save registers, with an lgkmcnt(0) behind every permute — two dozen
+// LDS round trips in a row with nothing to hide them under.
+template <int KSA, int KSB>
+__device__ __forceinline__ void exchange_sets(int h, int partner, const bf16x8 (&a0)[KSA], const bf16x8 (&a1)[KSA],
+                                              bf16x8 (&outa)[KSA][2], const bf16x8 (&b0)[KSB], const bf16x8 (&b1)[KSB],
+                                              bf16x8 (&outb)[KSB][2]) {
+    typedef int i32x4 __attribute__((ext_vector_type(4)));
+    constexpr int KS = KSA + KSB;
+    i32x4 s0[KS], s1[KS], send[KS], got[KS];
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+        s0[s] = __builtin_bit_cast(i32x4, s < KSA ? a0[s < KSA ? s : 0] : b0[s < KSA ? 0 : s - KSA]);
+        s1[s] = __builtin_bit_cast(i32x4, s < KSA ? a1[s < KSA ? s : 0] : b1[s < KSA ? 0 : s - KSA]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) send[s][j] = h ? s0[s][j] : s1[s][j];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int s = 0; s < KS; ++s)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) got[s][j] = __builtin_amdgcn_ds_bpermute(partner, send[s][j]);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+        i32x4 c0, c1;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            c0[j] = h ? got[s][j] : s0[s][j];
+            c1[j] = h ? s1[s][j] : got[s][j];
+        }
+        if (s < KSA) {
+            outa[s < KSA ? s : 0][0] = __builtin_bit_cast(bf16x8, c0);
+            outa[s < KSA ? s : 0][1] = __builtin_bit_cast(bf16x8, c1);
+        } else {
+            outb[s < KSA ? 0 : s - KSA][0] = __builtin_bit_cast(bf16x8, c0);
+            outb[s < KSA ? 0 : s - KSA][1] = __builtin_bit_cast(bf16x8, c1);
+        }
     }
 }
 

@@ -30,6 +30,11 @@
 namespace nfx {
 namespace v6 {
 
+// What a lane's encoders take of its point: depth, ray direction, ray origin.
+struct PointIn {
+    float zz, d[3], o[3];
+};
+
 template <int DMA, Seq S>
 __device__ __forceinline__ void nerf_mlp_bf16_v6_body(
     const float* __restrict__ rayo, const float* __restrict__ rayd, const float* __restrict__ zbuf, long long n_pts,
@@ -38,6 +43,7 @@ __device__ __forceinline__ void nerf_mlp_bf16_v6_body(
     using namespace nerf;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, p = lane & 31;
     constexpr bool FOLD = S == Seq::Render;
+    constexpr bool kAhead = DMA == 1;   // fetch the next point tile's inputs one tile ahead (below)
     float* bias_lds = floats_of<DMA, S>(smem);
     Acc accs[2];
     Pre pre;
@@ -45,23 +51,56 @@ __device__ __forceinline__ void nerf_mlp_bf16_v6_body(
     const Ctx cx = prologue<DMA, S>(smem, blob, FOLD ? nerf::fold::kWeightBytes : nerf::kWeightBytes, kBiasFloats, tid, lane, rg, pre,
                                     accs[0]);
     const long long n_tiles = (n_pts + kTilePts - 1) / kTilePts;
+    // The front end: ONE point per lane.  Lanes p and p + 32 hold the points of column tile 0 and 1 at column p; lane (h, p)
+    // fetches and encodes the point of column tile h, both slot sets of it, and trades the set of the other half with lane
+    // p ^ 32 (mlp_engine.hpp: posenc_sets, exchange_sets).  A lane whose own point lies past n_pts takes point n_pts - 1, encodes
+    // it and takes part in the exchange like every other lane: its partner may hold a valid point of the other column tile.
+    const int partner = (lane ^ 32) << 2;
+    // flat sample `mm` and ray `ray` of the lane's own point of point tile `tl`; a tile past the last one gives n_pts - 1
+    auto own_point = [&](long long tl, long long& mm_of, long long& ray_of) {
+        long long m[kCT];
+        const int c = h;
+        m[c] = tl * kTilePts + wave * (32 * kCT) + c * 32 + p;
+        const long long mm = m[c] < n_pts ? m[c] : n_pts - 1;
+        const long long ray = mm / n_samples;
+        mm_of = mm;
+        ray_of = ray;
+    };
+    auto fetch = [&](long long mm, long long ray, PointIn& in) {
+        in.zz = zbuf[mm];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            in.d[k] = rayd[ray * 3 + k];
+            in.o[k] = rayo[ray * 3 + k];
+        }
+    };
+    // The seven values of the lane's point of the NEXT point tile of this workgroup (tl + gridDim.x) are fetched during the pass
+    // and carried across the loop edge; where that tile does not exist every lane fetches point n_pts - 1 and nobody uses it.
+    PointIn ahead;
+    if constexpr (kAhead) {
+        long long mm, ray;
+        own_point(blockIdx.x, mm, ray);
+        fetch(mm, ray, ahead);
+    }
     for (long long tl = blockIdx.x; tl < n_tiles; tl += gridDim.x) {
         bf16x8 pe[4][kCT], pv[2][kCT];
         long long m[kCT];
 #pragma unroll
-        for (int c = 0; c < kCT; ++c) {
-            m[c] = tl * kTilePts + wave * (32 * kCT) + c * 32 + p;
-            const long long mm = m[c] < n_pts ? m[c] : n_pts - 1;
-            const long long ray = mm / n_samples;
-            const float zz = zbuf[mm];
-            float x[3], d[3];
+        for (int c = 0; c < kCT; ++c) m[c] = tl * kTilePts + wave * (32 * kCT) + c * 32 + p;
+        // the division stays up here, outside the one basic block of the tiles; only the loads move (below)
+        long long mm, ray;
+        own_point(kAhead ? tl + gridDim.x : tl, mm, ray);
+        PointIn in;
+        if constexpr (kAhead) in = ahead;
+        else fetch(mm, ray, in);
+        {
+            float x[3];
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                d[k] = rayd[ray * 3 + k];
-                x[k] = rayo[ray * 3 + k] + d[k] * zz;
-            }
-            posenc<10, kCT>(x, h, c, pe);
-            posenc<4, kCT>(d, h, c, pv);
+            for (int k = 0; k < 3; ++k) x[k] = in.o[k] + in.d[k] * in.zz;
+            bf16x8 e0[4], e1[4], w0[2], w1[2];
+            posenc_sets<10>(x, e0, e1);
+            posenc_sets<4>(in.d, w0, w1);
+            exchange_sets(h, partner, e0, e1, pe, w0, w1, pv);
         }
         bf16x8 ha[16][kCT], hb[16][kCT], r0[8][kCT];
         float sigma[kCT];
@@ -74,6 +113,14 @@ __device__ __forceinline__ void nerf_mlp_bf16_v6_body(
         // chunk index K: L0 0-7, L1-4 8-39, L5 40-47, L6-7 48-63, bottleneck 64-71, sigma 72, rgb0 73-76, rgb1 77
         // (folded: sigma 64, rgb0 65-68, rgb1 69); tile K accumulates in accs[K & 1]
         layer<0, 4, 0, 8, true, DMA, S>(cx, rg, bl, bl + 256 * 1, pe, pe, ha, accs, pre, EpiNone{});
+        if constexpr (kAhead) {
+            // Issued HERE, behind the short tiles of layer 0: vmcnt counts these three loads and the weight pieces together, in
+            // issue order, so the next counted wait of tile<> (end of tile 8) also waits for them — it is a full 16-k-step tile
+            // away.  (The waits can only wait for more with older loads in flight: they stay correct.)  The empty statement
+            // keeps the compiler from issuing the loads at the loop top, in front of tile 0's wait.
+            asm volatile("" : "+v"(mm), "+v"(ray));
+            fetch(mm, ray, ahead);
+        }
         layer<8, 16, 0, 8, true, DMA, S>(cx, rg, bl + 256 * 1, bl + 256 * 2, ha, pe, hb, accs, pre, pend(T{}, accs[1], ha[14], ha[15]));
         layer<16, 16, 0, 8, true, DMA, S>(cx, rg, bl + 256 * 2, bl + 256 * 3, hb, pe, ha, accs, pre, pend(T{}, accs[1], hb[14], hb[15]));
         layer<24, 16, 0, 8, true, DMA, S>(cx, rg, bl + 256 * 3, bl + 256 * 4, ha, pe, hb, accs, pre, pend(T{}, accs[1], ha[14], ha[15]));
@@ -105,6 +152,12 @@ __device__ __forceinline__ void nerf_mlp_bf16_v6_body(
         }
         // rgb_out[1] (K = 77 -> accs[1]); pending: last rgb_out[0] tile (K = 76 -> accs[0]); next: L0 tile 0
         tile<77, 8, 0, DMA, S>(cx, rg, bl, r0, pe, accs[1], accs[0], pre, pend(T{}, accs[0], r0[6], r0[7]));
+        }
+        if constexpr (kAhead) {
+            // the fetched values are taken over in front of the stores: behind them the compiler's wait for the loads would
+            // be a vmcnt(0) that also waits for the stores to be acknowledged
+            asm volatile("" : "+v"(ahead.zz), "+v"(ahead.d[0]), "+v"(ahead.d[1]), "+v"(ahead.d[2]), "+v"(ahead.o[0]),
+                         "+v"(ahead.o[1]), "+v"(ahead.o[2]));
         }
         if (h == 0) {
 #pragma unroll
