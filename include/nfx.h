@@ -388,6 +388,27 @@ NFX_API int nfx_isosurface_emit(const float *dev_field, int nx, int ny, int nz, 
                                 const float *spacing, const void *dev_workspace, size_t workspace_bytes, int64_t nv,
                                 int64_t nf, float *dev_vertices, int32_t *dev_faces, void *stream);
 
+/* Connected components of an indexed triangle mesh (csrc/mesh_components.hip).
+ *   Relation  two vertices are connected when a face names both; the relation is closed transitively.  dev_faces: int32
+ *             [nf, 3], dev_label: int32 [nv].
+ *   Labels    label[v] = the smallest vertex index of v's component; a vertex that no face names has label[v] = v.  The
+ *             labels are a function of the face SET: independent of the order of the faces, of the rotation of a face's
+ *             three indices, of duplicate faces and of degenerate ones ((a, a, b) connects a and b, (a, a, a) nothing);
+ *             the same bits on every run, whatever dev_label and the workspace held before.  Every element is written.
+ *   Skipped   a face with an index outside [0, nv) connects nothing and is never dereferenced (every index is checked
+ *             before it addresses memory); word 0 of the workspace (int32) receives the number of such faces, 0 for a
+ *             valid mesh.  Word 0 is written by every successful call; the caller reads it back.
+ *   Limits    0 <= nv < 2^31, 0 <= 3 nf < 2^31, dev_faces, dev_label and dev_workspace 16-byte aligned,
+ *             workspace_bytes >= nfx_mesh_components_workspace_bytes(nv, nf) (0 = counts outside the limits); refused
+ *             with their numbers before anything is launched.  nv = 0: no label is written; nf = 0: the identity.
+ *   Work      a lock-free union-find in dev_label itself: parent[v] = v; per face, the larger root is hooked under the
+ *             smaller by compare-and-swap (retried when it fails), paths halved on the way; a last launch stores every
+ *             vertex's root.  Three launches on `stream`, agent-scope integer atomics only, nothing allocated, no
+ *             synchronisation with the host.                                                                          */
+NFX_API size_t nfx_mesh_components_workspace_bytes(int64_t nv, int64_t nf);
+NFX_API int nfx_mesh_components(const int32_t *dev_faces, int64_t nf, int64_t nv, int32_t *dev_label,
+                                void *dev_workspace, size_t workspace_bytes, void *stream);
+
 /* Rusinkiewicz coordinates (phi_d, theta_h, theta_d), util/geom.py:152-192. a,b [n,3]. */
 NFX_API int nfx_dir2rusink(const float *dev_a, const float *dev_b, int64_t n, float *dev_rusink,
                    void *stream);

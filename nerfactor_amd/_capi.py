@@ -72,6 +72,8 @@ SIGNATURES = {
     'nfx_isosurface_workspace_bytes': (_sz, [_i, _i, _i]),
     'nfx_isosurface_count': (_i, [_p, _i, _i, _i, _f, _p, _sz, _p]),
     'nfx_isosurface_emit': (_i, [_p, _i, _i, _i, _f, _p, _p, _p, _sz, _i64, _i64, _p, _p, _p]),
+    'nfx_mesh_components_workspace_bytes': (_sz, [_i64, _i64]),
+    'nfx_mesh_components': (_i, [_p, _i64, _i64, _p, _p, _sz, _p]),
     'nfx_dir2rusink': (_i, [_p, _p, _i64, _p, _p]),
     'nfx_mlp128_train_packed_bytes': (_sz, [_i]),
     'nfx_mlp128_pack_train_weights': (_i, [_pp, _pp, _i, _i, _i, _p, _sz]),

@@ -1,5 +1,5 @@
-// capi_mesh.cpp — C-ABI entry points of the mesh BVH builder (mesh_bvh.cpp, host only), the ray casts (mesh_cast.hip) and the
-// iso-surface extraction (isosurface.hip).
+// capi_mesh.cpp — C-ABI entry points of the mesh BVH builder (mesh_bvh.cpp, host only), the ray casts (mesh_cast.hip), the
+// iso-surface extraction (isosurface.hip) and the component labelling (mesh_components.hip).
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -104,5 +104,23 @@ int nfx_isosurface_emit(const float* field, int nx, int ny, int nz, float iso, c
     return nfx_hip_result(nfx_launch_isosurface_emit(field, nx, ny, nz, iso, origin, spacing, workspace, (int)nv, (int)nf, vertices, faces,
                                                      (hipStream_t)stream),
                           "isosurface_emit");
+}
+
+size_t nfx_mesh_components_workspace_bytes(int64_t nv, int64_t nf) {
+    if (nv < 0 || nv >= (1ll << 31) || nf < 0 || 3 * nf >= (1ll << 31)) return 0;
+    return 16;   // word 0: the faces skipped; padded to the alignment
+}
+
+int nfx_mesh_components(const int32_t* faces, int64_t nf, int64_t nv, int32_t* label, void* workspace, size_t workspace_bytes, void* stream) {
+    REQUIRE(nv >= 0 && nv < (1ll << 31), "nfx_mesh_components: nv = %lld vertices (0 .. 2^31 - 1)", (long long)nv);
+    REQUIRE(nf >= 0 && nf < (1ll << 31) && 3 * nf < (1ll << 31), "nfx_mesh_components: nf = %lld triangles, 3 nf = %lld (below 2^31)",
+            (long long)nf, (long long)(3 * nf));
+    REQUIRE(workspace, "nfx_mesh_components: null workspace");
+    REQUIRE(workspace_bytes >= nfx_mesh_components_workspace_bytes(nv, nf), "nfx_mesh_components: workspace of %zu bytes, %zu needed",
+            workspace_bytes, nfx_mesh_components_workspace_bytes(nv, nf));
+    REQUIRE((nf == 0 || faces) && (nv == 0 || label), "nfx_mesh_components: null pointer");
+    if (!ALIGNED(faces, 16) || !ALIGNED(label, 16) || !ALIGNED(workspace, 16))
+        return nfx_fail(NFX_EALIGN, "nfx_mesh_components: faces, label and workspace must be 16-byte aligned");
+    return nfx_hip_result(nfx_launch_mesh_components(faces, nf, nv, label, (int*)workspace, (hipStream_t)stream), "mesh_components");
 }
 }

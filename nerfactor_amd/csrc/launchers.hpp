@@ -53,6 +53,8 @@ void nfx_isosurface_host_tables(int8_t* tri, int8_t* edge);
 int nfx_launch_isosurface_count(const float* field, int nx, int ny, int nz, float iso, void* ws, hipStream_t st);
 int nfx_launch_isosurface_emit(const float* field, int nx, int ny, int nz, float iso, const float* origin, const float* spacing,
                                const void* ws, int nv, int nf, float* vertices, int* faces, hipStream_t st);
+// ---- mesh_components.hip (label doubles as the parent array; skipped: word 0 of the workspace)
+int nfx_launch_mesh_components(const int* faces, long long nf, long long nv, int* label, int* skipped, hipStream_t st);
 // ---- loss.hip
 int nfx_launch_pair_loss(int bwd, const nfx_loss_term* terms, int n_terms, const float* alpha, float bg, long long n, float* loss,
                          const float* dloss, hipStream_t st);

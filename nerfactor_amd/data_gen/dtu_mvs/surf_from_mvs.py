@@ -3,6 +3,7 @@ reference's flags and output layout (data_gen/dtu_mvs/surf_from_mvs.py):
 
     python -m nerfactor_amd.data_gen.dtu_mvs.surf_from_mvs --cam_dir <dir> --surf_dir <dir> --img_dir <dir>/scanN --outdir <mvs_root> \\
         [--h 256] [--light_h 16] [--n_vali 2] [--n_test 120] [--lvis_eps 0.1] [--lvis_radius 1e5] [--nolvis] [--debug] [--overwrite]
+        [--keep_largest K] [--min_faces M]
 
     <outdir>/lights.npz                          lxyzs [h, 2h, 3] around the mesh centre with z flipped, lareas [h, 2h]
     <outdir>/{train,val}_###/                    metadata.json (id, imh, imw, cam_loc), rgba.png, alpha.png, xyz.{npy,png},
@@ -18,19 +19,22 @@ One deliberate difference: the reference ships with its gen_lvis calls commented
 this driver writes it unless --nolvis is given.  The reference's lvis.mp4 and debug video are not written.
 
 Camera rays and one shadow ray per (surface point, light) are cast on the GPU (mesh.RayMeshIntersector: nfx_mesh_cast,
-nfx_mesh_lvis with the rays made in the kernel); the [pixels, lights] visibility of a view is the only large allocation."""
+nfx_mesh_lvis with the rays made in the kernel); the [pixels, lights] visibility of a view is the only large allocation.
+--keep_largest K / --min_faces M (opt-in): the scan's connected components are labelled on the GPU (TriMesh.filter_components)
+and only the K with the most triangles / those with at least M triangles are cast against; vertices are not welded first."""
 import argparse
 import glob
 import json
 import os
 import shutil
 import sys
+import time
 from os.path import basename, isdir, join
 
 import numpy as np
 
 from ...brdf.renderer import gen_light_xyz
-from ...mesh import PerspCam, RayMeshIntersector, TriMesh, decompose_projection, sph2cart
+from ...mesh import PerspCam, RayMeshIntersector, TriMesh, decompose_projection, filter_clause, sph2cart
 from ...nerfactor.util.light import resize_antialias
 
 
@@ -47,6 +51,8 @@ def parse_args(argv=None):
     ap.add_argument('--lvis_eps', type=float, default=1e-1, help="offset of a shadow ray's origin along its direction")
     ap.add_argument('--lvis_radius', type=float, default=1e5, help="radius of the light sphere")
     ap.add_argument('--lvis_chunk', type=int, default=1 << 16, help="pixels per light-visibility launch")
+    ap.add_argument('--keep_largest', type=int, default=0, help="keep only the K connected components of the scan with the most triangles")
+    ap.add_argument('--min_faces', type=int, default=0, help="keep only the connected components of the scan with at least M triangles")
     ap.add_argument('--nolvis', action='store_true', help="skip light visibility (what the reference does as shipped)")
     ap.add_argument('--debug', action='store_true', help="first four views only")
     ap.add_argument('--overwrite', action='store_true', help="whether to remove output folder if it already exists")
@@ -133,6 +139,8 @@ def process_view(cam, mesh, inter, lxyz, args, outdir):
 
 def main(argv=None):
     args = parse_args(argv)
+    if args.keep_largest < 0 or args.min_faces < 0:
+        raise ValueError("surf_from_mvs: keep_largest = %d and min_faces = %d must not be negative" % (args.keep_largest, args.min_faces))
     import torch
     if not torch.cuda.is_available():
         raise RuntimeError("surf_from_mvs casts every ray on the GPU and needs an MI355X: libnfx has no CPU path")
@@ -151,6 +159,11 @@ def main(argv=None):
     ind_vali = vali_indices(n_imgs, args.n_vali)
 
     mesh = TriMesh.load(mesh_path_of(args.surf_dir, args.img_dir))
+    if args.keep_largest or args.min_faces:      # before the BVH is built
+        t0 = time.perf_counter()
+        mesh = mesh.filter_components(args.keep_largest, args.min_faces)
+        print("[surf_from_mvs] %s: %d vertices, %d triangles" % (filter_clause(mesh.filter_info, time.perf_counter() - t0),
+                                                               mesh.vertices.shape[0], mesh.faces.shape[0]), flush=True)
     inter = RayMeshIntersector(mesh)
 
     # DTU scenes are roughly 1000x bigger than normalised NeRF scenes and not centred at the origin, and their z axis is flipped

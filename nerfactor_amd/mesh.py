@@ -2,7 +2,8 @@
 data_gen/dtu_mvs/surf_from_mvs.py takes from trimesh (load, face_normals, ray.ray_pyembree.RayMeshIntersector), OpenCV
 (decomposeProjectionMatrix) and xiuminglib (camera.PerspCam, geometry.sph.sph2cart) in the reference.  The mesh, the tree
 build (ops.mesh_bvh_build, host code of libnfx) and the camera are host-side NumPy; every ray is cast by the two kernels of
-csrc/mesh_cast.hip (ops.mesh_cast, ops.mesh_lvis), which have no CPU path."""
+csrc/mesh_cast.hip (ops.mesh_cast, ops.mesh_lvis), which have no CPU path.  Connected components: the labels come from
+csrc/mesh_components.hip (ops.mesh_components); filter_by_labels, which selects and re-indexes, is plain torch."""
 import numpy as np
 
 _PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': 'i2', 'int16': 'i2', 'ushort': 'u2', 'uint16': 'u2',
@@ -108,6 +109,80 @@ def write_ply(path, vertices, faces, binary=True, normals=None):
                 h.write(('3 %d %d %d\n' % tuple(int(x) for x in row)).encode('ascii'))
 
 
+def check_filter(keep_largest, min_faces):
+    """(K, M) as ints of a component filter; a negative number, or no criterion at all, is refused."""
+    try:
+        k, m = int(keep_largest), int(min_faces)
+        exact = k == keep_largest and m == min_faces
+    except (TypeError, ValueError):
+        exact = False
+    if not exact or k < 0 or m < 0:
+        raise ValueError("component filter: keep_largest = %r and min_faces = %r must be integers >= 0" % (keep_largest, min_faces))
+    if k == 0 and m == 0:
+        raise ValueError("component filter: keep_largest = 0 and min_faces = 0 keep every component: give one of them")
+    return k, m
+
+
+def filter_by_labels(vertices, faces, label, keep_largest=0, min_faces=0, attrs=()):
+    """(vertices', faces', attrs', info): the mesh without the components that fail the filter.  Pure torch on the tensors'
+    own device (CPU tensors work).  vertices [nv, 3], faces integer [nf, 3], label integer [nv] with label[v] = the smallest
+    vertex index of v's component (ops.mesh_components), attrs: per-vertex tensors [nv, k].
+
+    A face belongs to the component of its first vertex; a component's size is its number of faces, duplicate and degenerate
+    faces included.  keep_largest = K >= 1 keeps the K components with the most faces (equal sizes: the smaller label first),
+    min_faces = M >= 1 those with at least M faces; with both a component must pass both; with neither the call is refused.
+    A vertex survives if and only if a surviving face names it, so vertices that no face names are always dropped.  Surviving
+    vertices and faces keep their relative order; the faces are re-indexed, the attrs gathered with the same index.  A filter
+    that keeps nothing returns (0, 3) shapes.
+    info: n_components (with at least one face), n_unreferenced (vertices that no face names), kept = [(label, faces,
+    vertices)] in ascending label order, dropped_faces, dropped_vertices, vertex_index (int64 tensor: the old index of every
+    surviving vertex).
+    Vertices are not welded: a triangle soup (every triangle with three vertices of its own) has one component per triangle."""
+    import torch
+    k, m = check_filter(keep_largest, min_faces)
+    if vertices.dim() != 2 or faces.dim() != 2 or faces.shape[1] != 3 or label.dim() != 1 or label.shape[0] != vertices.shape[0]:
+        raise ValueError("filter_by_labels: vertices [nv, 3], faces [nf, 3] and label [nv] are expected, got %s, %s and %s"
+                         % (tuple(vertices.shape), tuple(faces.shape), tuple(label.shape)))
+    attrs = tuple(attrs)
+    for a in attrs:
+        if a.shape[0] != vertices.shape[0]:
+            raise ValueError("filter_by_labels: an attribute of %d rows for %d vertices" % (a.shape[0], vertices.shape[0]))
+    nv, nf = vertices.shape[0], faces.shape[0]
+    if nf and (int(faces.min()) < 0 or int(faces.max()) >= nv):
+        raise ValueError("filter_by_labels: a face names a vertex outside [0, %d)" % nv)
+    idx = faces.long()
+    face_label = label.long()[idx[:, 0]]
+    comp, sizes = torch.unique(face_label, return_counts=True)          # ascending labels
+    keep = torch.ones_like(comp, dtype=torch.bool)
+    if m:
+        keep &= sizes >= m
+    if k:
+        top = torch.zeros_like(keep)
+        top[torch.sort(sizes, descending=True, stable=True).indices[:k]] = True    # stable: equal sizes in label order
+        keep &= top
+    keep_face = keep[torch.searchsorted(comp, face_label)]
+    idx = idx[keep_face]
+    referenced = torch.zeros(nv, dtype=torch.bool, device=faces.device)
+    referenced[faces.long().reshape(-1)] = True
+    keep_vertex = torch.zeros(nv, dtype=torch.bool, device=faces.device)
+    keep_vertex[idx.reshape(-1)] = True
+    vertex_index = keep_vertex.nonzero()[:, 0]
+    new_index = torch.cumsum(keep_vertex, 0) - 1
+    kept_label, kept_vertices = torch.unique(label.long()[vertex_index], return_counts=True)
+    info = {'n_components': int(comp.numel()), 'n_unreferenced': nv - int(referenced.sum()),
+            'kept': list(zip(kept_label.tolist(), sizes[keep].tolist(), kept_vertices.tolist())),
+            'dropped_faces': nf - int(idx.shape[0]), 'dropped_vertices': nv - int(vertex_index.numel()),
+            'vertex_index': vertex_index}
+    return vertices[vertex_index], new_index[idx].to(faces.dtype), tuple(a[vertex_index] for a in attrs), info
+
+
+def filter_clause(info, seconds=None):
+    """The drivers' log clause of a component filter."""
+    text = "%d components, %d kept, %d triangles and %d vertices dropped" % (info['n_components'], len(info['kept']),
+                                                                             info['dropped_faces'], info['dropped_vertices'])
+    return text if seconds is None else text + ", components %.3f s" % seconds
+
+
 class TriMesh:
     """vertices [nv, 3] float64 and faces [nf, 3] int32 with trimesh's face normals; the kernels see the vertices as float32."""
 
@@ -130,6 +205,24 @@ class TriMesh:
             length = np.linalg.norm(n, axis=1, keepdims=True)
             self._normals = np.divide(n, length, out=np.zeros_like(n), where=length > 0)
         return self._normals
+
+    def filter_components(self, keep_largest=0, min_faces=0, device=None):
+        """A new TriMesh without the components that fail the filter (filter_by_labels' rules; its info as `.filter_info`):
+        the faces are uploaded, labelled on the GPU (ops.mesh_components) and the labels downloaded.  Vertices are not welded
+        first: a PLY stored as a triangle soup has one component per triangle."""
+        import torch
+        from . import ops
+        check_filter(keep_largest, min_faces)
+        if device is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError("labelling components needs an MI355X: libnfx has no CPU path")
+            from . import dist as nfx_dist
+            device = nfx_dist.local_device()
+        label = ops.mesh_components(torch.from_numpy(self.faces).to(device).contiguous(), self.vertices.shape[0]).cpu()
+        v, f, _, info = filter_by_labels(torch.from_numpy(self.vertices), torch.from_numpy(self.faces), label, keep_largest, min_faces)
+        out = TriMesh(v.numpy(), f.numpy())
+        out.filter_info = info
+        return out
 
     def bvh(self, max_leaf=4, device=None):
         """(blob on the device, its 32-byte header on the host); built and uploaded once per (max_leaf, device)."""

@@ -5,6 +5,7 @@ outputs (nerfactor/geometry_from_nerf.py:30-391):
         --trained_nerf=<outroot>/<xname> --out_root=<dir> [--imh H] [--scene_bbox x0,x1,y0,y1,z0,z1]
         [--lvis_far 1] [--occu_thres 0] [--light_h 16] [--spp 1] [--debug]
         [--occupancy_grid R [--grid_margin 10] [--grid_dilate 2] [--grid_probes 4] [--grid_check K]]
+        [--lvis_mesh mesh.ply [--lvis_mesh_eps 0.1]]
 
 For every view of every split writes <out_root>/<view id>/{alpha.png, xyz.npy, xyz.png, normal.npy, normal.png,
 lvis.npy, lvis.png} — what datasets/nerf_shape.py reads.  All marching runs on libnfx:
@@ -18,7 +19,12 @@ With N ranks the rays of EVERY view are split into N contiguous ranges (SURVEY.m
 writes its rows of the .npy files; rank 0 receives uint8 preview rows only.
 --occupancy_grid R (opt-in, occupancy.py): the density-only passes (the coarse pass of the camera rays, both passes of the
 shadow rays) evaluate only the samples whose cell of an R^3 grid baked from the NeRF may hold density — the same outputs
-wherever no skipped sample has a density (--grid_check K proves that on the scene)."""
+wherever no skipped sample has a density (--grid_check K proves that on the scene).
+--lvis_mesh PATH.ply (opt-in): light visibility from ONE shadow ray per (surface point, front-lit
+light) against a triangle mesh — the NeRF's own, written by mesh_from_nerf, best with --keep_largest 1 — instead of the
+density march (nfx_mesh_lvis).  Depth, normals and alpha still come from the camera march.  Three differences from the
+march: the visibility is binary (0 or alpha, not 1 - occupancy); the ray is unbounded (not cut at --lvis_far); the occluder
+is the mesh's level set, not the density field."""
 import argparse
 import glob
 import os
@@ -31,6 +37,7 @@ import torch
 from PIL import Image
 
 from .. import dist as nfx_dist
+from .. import mesh as nfx_mesh
 from ..brdf.renderer import gen_light_xyz
 from . import datasets, models, occupancy
 from .util import config as configutil
@@ -51,6 +58,13 @@ def parse_args(argv=None):
     ap.add_argument('--spp', type=int, default=1, help="samples per pixel")
     ap.add_argument('--fps', type=int, default=12, help="accepted for compatibility (no video is written)")
     ap.add_argument('--debug', action='store_true')
+    ap.add_argument('--lvis_mesh', default=None,
+                    help="PLY of the scene (mesh_from_nerf, best with --keep_largest 1): light visibility from one shadow ray per "
+                         "(surface point, light) against this mesh instead of the density march.  Unlike the march's, this "
+                         "visibility is binary (0 or alpha, not 1 - occupancy), its ray is unbounded (not cut at --lvis_far) and "
+                         "its occluder is the mesh's level set, not the density field")
+    ap.add_argument('--lvis_mesh_eps', type=float, default=.1,
+                    help="offset of a mesh shadow ray's origin along its direction (the march starts at the same 0.1)")
     occupancy.add_arguments(ap)
     return ap.parse_args(argv)
 
@@ -130,6 +144,38 @@ def compute_light_visibility(model, surf, normal, config, lvis_far=1., light_h=1
     return lvis
 
 
+def check_lvis_mesh(path, eps):
+    """Refusals of --lvis_mesh / --lvis_mesh_eps that need no GPU; returns the loaded mesh.TriMesh (None without a path)."""
+    if path is None:
+        return None
+    if not (np.isfinite(float(eps)) and float(eps) > 0):
+        raise ValueError("geometry_from_nerf: --lvis_mesh_eps = %r must be finite and positive" % (eps,))
+    if not os.path.isfile(path):
+        raise FileNotFoundError("geometry_from_nerf: --lvis_mesh %s: no such file" % path)
+    try:
+        mesh = nfx_mesh.TriMesh.load(path)
+    except (ValueError, KeyError, IndexError) as e:
+        raise ValueError("geometry_from_nerf: --lvis_mesh %s cannot be read: %s" % (path, e)) from e
+    if mesh.faces.shape[0] == 0:
+        raise ValueError("geometry_from_nerf: --lvis_mesh %s holds no triangle" % path)
+    return mesh
+
+
+def compute_light_visibility_mesh(intersector, surf, normal, light_h=16, eps=.1, chunk=1 << 16):
+    """lvis[n_surf, n_lights] from one shadow ray per pair against a mesh (mesh.RayMeshIntersector.light_visibility):
+    1 where the light is in front of the surface (normal . dir > 0) and the ray from surf + eps dir hits no triangle, else 0.
+    The lights are compute_light_visibility's."""
+    lxyz, _ = gen_light_xyz(light_h, 2 * light_h)
+    lxyz = torch.as_tensor(lxyz.reshape(-1, 3).astype(np.float32), device=surf.device)
+    surf, normal = surf.contiguous(), normal.contiguous()
+    n = surf.shape[0]
+    ones = torch.ones((n,), dtype=torch.float32, device=surf.device)
+    lvis = torch.empty((n, lxyz.shape[0]), dtype=torch.float32, device=surf.device)
+    for lo in range(0, n, chunk):
+        intersector.light_visibility(surf[lo:lo + chunk], normal[lo:lo + chunk], ones[lo:lo + chunk], lxyz, eps, out=lvis[lo:lo + chunk])
+    return lvis
+
+
 def average_supersamples(t, sps):
     return torch.stack([t[i::sps, j::sps] for i in range(sps) for j in range(sps)]).mean(0)
 
@@ -144,7 +190,7 @@ def _write_png(path, arr):
     Image.fromarray(arr).save(path)
 
 
-def process_view(config, model, batch, args, bbox, grid=None):
+def process_view(config, model, batch, args, bbox, grid=None, intersector=None):
     sps = int(np.sqrt(args.spp))
     id_, hw, rayo, rayd, _ = batch
     id_ = id_[0]
@@ -178,8 +224,12 @@ def process_view(config, model, batch, args, bbox, grid=None):
     n_lights = 2 * args.light_h * args.light_h
     lvis = torch.zeros((hi - lo, n_lights), device=rayo.device)
     if bool(hit.any()):
-        lvis_hit = compute_light_visibility(model, surf[hit], exp_normal[hit], config, lvis_far=args.lvis_far,
-                                            light_h=args.light_h, bbox=bbox, mlp_chunk=args.mlp_chunk, grid=grid)
+        if intersector is not None:
+            lvis_hit = compute_light_visibility_mesh(intersector, surf[hit], exp_normal[hit], light_h=args.light_h,
+                                                     eps=args.lvis_mesh_eps)
+        else:
+            lvis_hit = compute_light_visibility(model, surf[hit], exp_normal[hit], config, lvis_far=args.lvis_far,
+                                                light_h=args.light_h, bbox=bbox, mlp_chunk=args.mlp_chunk, grid=grid)
         lvis[hit] = lvis_hit.clamp(0., 1.)
     lvis = lvis * alpha[:, None]
     occupancy.log_view(grid, id_, 'geometry_from_nerf')
@@ -224,6 +274,7 @@ def _global_min_max(t):
 def main(argv=None):
     args = parse_args(argv)
     occupancy.check_arguments(args)
+    lvis_mesh = check_lvis_mesh(args.lvis_mesh, args.lvis_mesh_eps)      # every rank loads it once
     if not torch.cuda.is_available():
         raise RuntimeError("geometry_from_nerf needs an MI355X: libnfx has no CPU path")
     if int(np.sqrt(args.spp)) ** 2 != args.spp:
@@ -246,6 +297,12 @@ def main(argv=None):
     configutil.restore_model(model, ckpt)
     model.to(device)
     grid = occupancy.from_arguments(args, model, bbox, config.get('DEFAULT', 'data_root'))
+    intersector = nfx_mesh.RayMeshIntersector(lvis_mesh, device=device) if lvis_mesh is not None else None
+    if intersector is not None:
+        lvis_mesh.bvh(intersector.max_leaf, device)                       # the host build and the upload, once per process
+        if rank == 0:
+            print("[geometry_from_nerf] light visibility from %s: %d vertices, %d triangles, eps %g"
+                  % (args.lvis_mesh, lvis_mesh.vertices.shape[0], lvis_mesh.faces.shape[0], args.lvis_mesh_eps), flush=True)
     Dataset = datasets.get_dataset_class(config.get('DEFAULT', 'dataset'))
     done, i = [], 0
     with torch.no_grad():
@@ -255,7 +312,7 @@ def main(argv=None):
             except FileNotFoundError:
                 continue
             for batch in dataset.build_pipeline(no_batch=config.getboolean('DEFAULT', 'no_batch'), no_shuffle=True):
-                done.append(process_view(config, model, batch, args, bbox, grid))   # every rank: its rays of this view
+                done.append(process_view(config, model, batch, args, bbox, grid, intersector))   # every rank: its rays of this view
                 i += 1
                 if args.debug:
                     break

@@ -2,6 +2,7 @@
 
     python -m nerfactor_amd.nerfactor.mesh_from_nerf --trained_nerf=<outroot>/<xname>
         [--scene_bbox x0,x1,y0,y1,z0,z1] [--res 256] [--iso 10] [--network coarse|fine] [--nonormals] [--out mesh.ply]
+        [--keep_largest K] [--min_faces M]
 
 Three steps, all on libnfx: the network's raw density (before the relu) on a lattice of res^3 points over the box — the
 probe lattice of the occupancy grid, evaluated in chunks with nfx_nerf_sigma_fwd in the model's precision, as
@@ -10,6 +11,9 @@ stays inside the box, inside = density above iso, faces wound so that their norm
 -normalize(grad sigma) from nfx_nerf_sigma_grad (the face normals' sum where that gradient is zero).  The PLY
 (mesh.write_ply, float x y z nx ny nz) loads back through mesh.TriMesh.load, whose ray casts (mesh.RayMeshIntersector)
 then run against the NeRF's geometry.
+--keep_largest K / --min_faces M (opt-in): the mesh's connected components are labelled on the GPU
+(ops.mesh_components) and only the K with the most triangles / those with at least M triangles are written — a fitted
+density has floaters, and every one of them casts shadows; the normals are then evaluated at the surviving vertices only.
 With several ranks rank 0 alone extracts; the others wait."""
 import argparse
 import sys
@@ -39,12 +43,17 @@ def parse_args(argv=None):
                          "scene here: a network whose density peaks lower needs a lower level")
     ap.add_argument('--network', choices=sorted(NETWORKS), default='fine')
     ap.add_argument('--nonormals', action='store_true', help="write no per-vertex normals")
-    ap.add_argument('--out', default=None, help="output PLY (default: <trained_nerf>/mesh_<network>_res<R>_iso<iso>.ply)")
+    ap.add_argument('--keep_largest', type=int, default=0, help="keep only the K connected components with the most triangles (0: all)")
+    ap.add_argument('--min_faces', type=int, default=0, help="keep only the connected components with at least M triangles (0: all)")
+    ap.add_argument('--out', default=None, help="output PLY (default: <trained_nerf>/mesh_<network>_res<R>_iso<iso>.ply, with "
+                                                "_largest<K> and _min<M> before .ply when the components are filtered)")
     return ap.parse_args(argv)
 
 
-def check_lattice(box, res, iso):
+def check_lattice(box, res, iso, keep_largest=0, min_faces=0):
     """Refusals that need no GPU; returns the box as six floats."""
+    if int(keep_largest) < 0 or int(min_faces) < 0:
+        raise ValueError("mesh_from_nerf: keep_largest = %s and min_faces = %s must not be negative" % (keep_largest, min_faces))
     box = [float(v) for v in box]
     if len(box) != 6:
         raise ValueError("mesh_from_nerf: box = x_min,x_max,y_min,y_max,z_min,z_max, got %d numbers" % len(box))
@@ -106,12 +115,14 @@ def gradient_normals(nerf_model, vertices, network='fine', chunk=1 << 22):
     return normals
 
 
-def extract(nerf_model, box, res, iso=10., network='fine', normals=True, times=None):
+def extract(nerf_model, box, res, iso=10., network='fine', normals=True, times=None, keep_largest=0, min_faces=0, info=None):
     """(vertices float32 [nv, 3], faces int32 [nf, 3], normals float32 [nv, 3] or None) as NumPy arrays: the surface
-    sigma_raw = iso of the `network` of a tuned NeRF over `box`, sampled at res points per axis."""
+    sigma_raw = iso of the `network` of a tuned NeRF over `box`, sampled at res points per axis.  With keep_largest or
+    min_faces only the components that pass (mesh.filter_by_labels), filtered on the device before the normals; the dict
+    `info` then receives the filter's counts."""
     if network not in NETWORKS:
         raise ValueError("mesh_from_nerf: network = %r (coarse, fine)" % (network,))
-    box, res = check_lattice(box, res, iso), int(res)
+    box, res = check_lattice(box, res, iso, keep_largest, min_faces), int(res)
     occupancy.require_tuned(nerf_model)
     device = next(nerf_model.parameters()).device
     clock = _Clock(device, times)
@@ -120,6 +131,11 @@ def extract(nerf_model, box, res, iso=10., network='fine', normals=True, times=N
     origin, spacing = lattice_frame(box, res)
     vertices, faces = ops.isosurface(field, float(iso), origin, spacing)
     clock.lap('isosurface')
+    if keep_largest or min_faces:
+        vertices, faces, _, found = ops.mesh_filter_components(vertices, faces, keep_largest, min_faces)
+        if info is not None:
+            info.update(found)
+        clock.lap('components')
     nrm = gradient_normals(nerf_model, vertices, network).cpu().numpy() if normals else None
     vertices, faces = vertices.cpu().numpy(), faces.cpu().numpy()
     if normals:      # where the gradient is zero: the normalised sum of the adjacent face normals
@@ -146,8 +162,9 @@ class _Clock:
         self.t0 = t
 
 
-def default_out(trained_nerf, network, res, iso):
-    return join(trained_nerf, 'mesh_%s_res%d_iso%g.ply' % (network, res, iso))
+def default_out(trained_nerf, network, res, iso, keep_largest=0, min_faces=0):
+    suffix = ('_largest%d' % keep_largest if keep_largest else '') + ('_min%d' % min_faces if min_faces else '')
+    return join(trained_nerf, 'mesh_%s_res%d_iso%g%s.ply' % (network, res, iso, suffix))
 
 
 def main(argv=None):
@@ -161,12 +178,12 @@ def main(argv=None):
             bbox = [float(x) for x in args.scene_bbox.split(',')]
         except ValueError:
             raise ValueError("--scene_bbox %s: x_min,x_max,y_min,y_max,z_min,z_max" % args.scene_bbox) from None
-    check_lattice(bbox if bbox is not None else [0., 1.] * 3, args.res, args.iso)
+    check_lattice(bbox if bbox is not None else [0., 1.] * 3, args.res, args.iso, args.keep_largest, args.min_faces)
     if not torch.cuda.is_available():
         raise RuntimeError("mesh_from_nerf needs an MI355X: libnfx has no CPU path")
     device = nfx_dist.local_device()
     rank, _ = nfx_dist.init_from_env(device=device)
-    out = args.out or default_out(args.trained_nerf, args.network, args.res, args.iso)
+    out = args.out or default_out(args.trained_nerf, args.network, args.res, args.iso, args.keep_largest, args.min_faces)
     if rank == 0:
         ckpt = latest_checkpoint(args.trained_nerf)
         config = configutil.read_config(configutil.get_config_ini(ckpt))
@@ -176,12 +193,14 @@ def main(argv=None):
         configutil.restore_model(model, ckpt)
         model.to(device)
         box = bbox if bbox is not None else occupancy.cameras_box(config.get('DEFAULT', 'data_root'))
-        times = {}
-        vertices, faces, normals = extract(model, box, args.res, args.iso, args.network, not args.nonormals, times)
+        times, found = {}, {}
+        vertices, faces, normals = extract(model, box, args.res, args.iso, args.network, not args.nonormals, times,
+                                           args.keep_largest, args.min_faces, found)
         nfx_mesh.write_ply(out, vertices, faces, normals=normals)
-        print("[mesh_from_nerf] %d^3 lattice over %s, iso %g (%s network): %d vertices, %d triangles; lattice %.3f s, "
+        filtered = "; " + nfx_mesh.filter_clause(found, times['components']) if found else ""
+        print("[mesh_from_nerf] %d^3 lattice over %s, iso %g (%s network): %d vertices, %d triangles%s; lattice %.3f s, "
               "iso-surface %.3f s, normals %.3f s -> %s" % (args.res, [round(v, 6) for v in box], args.iso, args.network,
-                                                           vertices.shape[0], faces.shape[0], times['lattice'],
+                                                           vertices.shape[0], faces.shape[0], filtered, times['lattice'],
                                                            times['isosurface'], times['normals'], out), flush=True)
     nfx_dist.barrier()
     return out

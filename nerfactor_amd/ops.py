@@ -953,6 +953,55 @@ def isosurface(field, iso, origin=(0., 0., 0.), spacing=(1., 1., 1.)):
     return isosurface_emit(field, iso, origin, spacing, ws, nv, nf)
 
 
+# ------------------------------------------------------------------------------ mesh components
+def mesh_components(faces, nv, label=None, ws=None):
+    """label int32 [nv] on the device: per vertex the smallest vertex index of its connected component, two vertices being
+    connected when a face names both (nfx_mesh_components; a vertex that no face names keeps its own index).  faces: a
+    contiguous CUDA int32 [nf, 3] tensor.  A face index outside [0, nv) raises with the numbers BEFORE anything is launched
+    (two reductions in torch); the kernel's own count of skipped faces is read back afterwards and raises too.  `label` and
+    `ws` (int32, at least 4 words) may be passed in; what they hold does not matter.
+    Vertices are NOT welded: a mesh stored as a triangle soup has one component per triangle (ops.isosurface meshes are
+    indexed, every vertex once)."""
+    if not (isinstance(faces, torch.Tensor) and faces.is_cuda and faces.dtype == torch.int32 and faces.is_contiguous()
+            and faces.dim() == 2 and faces.shape[1] == 3):
+        raise _capi.NfxError("mesh_components: faces must be a contiguous CUDA/ROCm int32 [nf, 3] tensor (libnfx has no CPU path)")
+    nv, nf = int(nv), int(faces.shape[0])
+    nbytes = lib.nfx_mesh_components_workspace_bytes(nv, nf)
+    if nbytes == 0:
+        raise _capi.NfxError("mesh_components: nv = %d vertices, nf = %d triangles (0 <= nv < 2^31 and 0 <= 3 nf = %d < 2^31)"
+                             % (nv, nf, 3 * nf))
+    if nf:
+        lo, hi = (int(x) for x in torch.stack((faces.amin(), faces.amax())).tolist())
+        if lo < 0 or hi >= nv:
+            raise _capi.NfxError("mesh_components: the faces name vertices %d .. %d, outside [0, %d)" % (lo, hi, nv))
+    if label is None:
+        label = torch.empty((nv,), dtype=torch.int32, device=faces.device)
+    elif not (isinstance(label, torch.Tensor) and label.is_cuda and label.dtype == torch.int32 and label.is_contiguous()
+              and tuple(label.shape) == (nv,)):
+        raise _capi.NfxError("mesh_components: `label` must be a contiguous CUDA int32 [%d] tensor" % nv)
+    if ws is None:
+        ws = torch.empty((nbytes // 4,), dtype=torch.int32, device=faces.device)
+    elif not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.dtype == torch.int32 and ws.is_contiguous() and ws.numel() * 4 >= nbytes):
+        raise _capi.NfxError("mesh_components: the workspace must be a contiguous CUDA int32 tensor of at least %d words" % (nbytes // 4))
+    check(lib.nfx_mesh_components(_ptr(faces), nf, nv, _ptr(label), _ptr(ws), ws.numel() * 4, _stream()), 'nfx_mesh_components')
+    skipped = int(ws[0])
+    if skipped:
+        raise _capi.NfxError("mesh_components: %d of %d faces name a vertex outside [0, %d) and were skipped" % (skipped, nf, nv))
+    return label
+
+
+def mesh_filter_components(vertices, faces, keep_largest=0, min_faces=0, attrs=()):
+    """(vertices', faces', attrs', info) on the device: the mesh without the components that fail the filter — labelled by
+    mesh_components, selected and re-indexed by mesh.filter_by_labels (its rules and its `info`).  vertices [nv, 3] and the
+    per-vertex attrs [nv, k] are CUDA tensors, faces a contiguous CUDA int32 [nf, 3] tensor."""
+    from . import mesh as nfx_mesh
+    if not (isinstance(vertices, torch.Tensor) and vertices.is_cuda and vertices.dim() == 2):
+        raise _capi.NfxError("mesh_filter_components: vertices must be a CUDA/ROCm [nv, 3] tensor")
+    nfx_mesh.check_filter(keep_largest, min_faces)
+    label = mesh_components(faces, vertices.shape[0])
+    return nfx_mesh.filter_by_labels(vertices, faces, label, keep_largest, min_faces, attrs)
+
+
 def _shade_common(xyz, cam, normal, albedo, rough, spec, lvis, lxyz, lareas, lvis_row=None):
     xyz = _dev(xyz, 'xyz', (None, 3))
     n = xyz.shape[0]
