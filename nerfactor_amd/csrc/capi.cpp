@@ -1,5 +1,5 @@
 // capi.cpp — the C-ABI of libnfx.so (include/nfx.h): argument validation, error reporting and
-// dispatch to the kernel launchers.  No device allocation, no synchronisation.
+// dispatch to the kernel launchers.  No device allocation, no synchronisation.  (The weight packers: pack_nets.cpp.)
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -7,12 +7,10 @@
 #include <string.h>
 
 #include <atomic>
-#include <vector>
 
 #include "capi_common.hpp"
 #include "nerf_layout.hpp"
 #include "nerf_fold_layout.hpp"
-#include "pack.hpp"
 
 static thread_local char g_err[512] = "";
 
@@ -112,67 +110,6 @@ int nfx_get_option(const char* key, int* value, int* is_set) {
     if (!o || !value) return nfx_fail(NFX_EINVAL, "nfx_get_option: unknown option '%s' or null output", key ? key : "(null)");
     *value = o->value.load(std::memory_order_relaxed);
     if (is_set) *is_set = o->is_set.load(std::memory_order_acquire);
-    return NFX_OK;
-}
-
-// --------------------------------------------------------------------------- packing
-size_t nfx_nerf_packed_bytes(int prec) {
-    if (prec == NFX_PREC_BF16) return nfx::nerf::kBlobBytes;
-    if (prec == NFX_PREC_FP32) return (size_t)nfx::nerf::kBlobBytes + nfx::nerf::kWeightBytes;  // hi | lo | biases
-    return 0;
-}
-
-// bf16 fragments of the 12 layers into w (nerf::kWeightBytes), biases into b (nerf::kBiasFloats)
-static int pack_nerf_fragments(const float* const kernels[12], const float* const biases[12], uint8_t* w0, float* b) {
-    using namespace nfx;
-    using namespace nfx::pack;
-    uint8_t* w = w0;
-    const Seg pe_xyz{kPosEnc, 10, 0, nullptr};
-    const Seg hid256{kHidden, 256, 0, nullptr};
-    // enc[0]: posenc(xyz) 63 -> 256
-    w += pack_layer_bf16({pe_xyz}, {{kernels[0], biases[0], 256}}, 8, 8, w, b + nerf::kBiasL0);
-    for (int l = 1; l <= 7; ++l) {
-        float* bl = b + nerf::kBiasL0 + 256 * l;
-        if (l == 5) {  // input = concat(y[256], posenc(xyz)[63])   (mlp.py:47-48)
-            const Seg pe_skip{kPosEnc, 10, 256, nullptr};
-            w += pack_layer_bf16({hid256, pe_skip}, {{kernels[5], biases[5], 256}}, 8, 24, w, bl);
-        } else {
-            w += pack_layer_bf16({hid256}, {{kernels[l], biases[l], 256}}, 8, 16, w, bl);
-        }
-    }
-    // fused [bottleneck (256 cols) | sigma_out (1 col)] on the encoder output
-    w += pack_layer_bf16({hid256}, {{kernels[9], biases[9], 256}, {kernels[8], biases[8], 1}}, 9, 16, w,
-                         b + nerf::kBiasBott);
-    // rgb_out[0]: concat(bottleneck[256], posenc(view)[27]) -> 128
-    const Seg pe_view{kPosEnc, 4, 256, nullptr};
-    w += pack_layer_bf16({hid256, pe_view}, {{kernels[10], biases[10], 128}}, 4, 24, w, b + nerf::kBiasRgb0);
-    // rgb_out[1]: 128 -> 3
-    const Seg hid128{kHidden, 128, 0, nullptr};
-    w += pack_layer_bf16({hid128}, {{kernels[11], biases[11], 3}}, 1, 8, w, b + nerf::kBiasRgb1);
-    return w == w0 + nerf::kWeightBytes ? NFX_OK : NFX_EINVAL;
-}
-
-int nfx_nerf_pack_weights(const float* const kernels[12], const float* const biases[12], int prec,
-                          void* blob, size_t blob_bytes) {
-    using namespace nfx;
-    REQUIRE(kernels && biases && blob, "nfx_nerf_pack_weights: null argument");
-    for (int i = 0; i < 12; ++i) REQUIRE(kernels[i] && biases[i], "nfx_nerf_pack_weights: layer %d null", i);
-    REQUIRE(prec == NFX_PREC_BF16 || prec == NFX_PREC_FP32, "nfx_nerf_pack_weights: bad prec %d", prec);
-    REQUIRE(blob_bytes >= nfx_nerf_packed_bytes(prec), "nfx_nerf_pack_weights: blob too small (%zu < %zu)",
-            blob_bytes, nfx_nerf_packed_bytes(prec));
-    uint8_t* w = static_cast<uint8_t*>(blob);
-    if (prec == NFX_PREC_BF16) {
-        if (pack_nerf_fragments(kernels, biases, w, reinterpret_cast<float*>(w + nerf::kWeightBytes)))
-            return nfx_fail(NFX_EINVAL, "nfx_nerf_pack_weights: internal layout mismatch");
-        return NFX_OK;
-    }
-    // NFX_PREC_FP32 (nerf_mlp_x3.hip): [fragments of hi = bf16(W) | fragments of lo = bf16(W - hi) | fp32 biases]
-    const pack::LoKernels lo = pack::lo_kernels(kernels, pack::kNerfShapes, 12);
-    float* b = reinterpret_cast<float*>(w + 2 * (size_t)nerf::kWeightBytes);
-    std::vector<float> sink(nerf::kBiasFloats);
-    if (pack_nerf_fragments(kernels, biases, w, b) ||
-        pack_nerf_fragments(lo.ptr.data(), biases, w + nerf::kWeightBytes, sink.data()))
-        return nfx_fail(NFX_EINVAL, "nfx_nerf_pack_weights: internal layout mismatch");
     return NFX_OK;
 }
 

@@ -16,3 +16,5 @@ int nfx_hip_result(int e, const char* what);    // NFX_OK, or NFX_EHIP with HIP'
 inline int in_dims_of(int in_kind, int z_dim) {
     return in_kind == NFX_IN_XYZ ? 63 : in_kind == NFX_IN_XYZ_LDIR ? 90 : in_kind == NFX_IN_Z_RUSINK ? z_dim + 15 : -1;
 }
+// the kinds with a training blob and a backward of their own (the learned BRDF has its own entry points)
+inline bool m128_has_backward(int in_kind) { return in_kind == NFX_IN_XYZ || in_kind == NFX_IN_XYZ_LDIR; }

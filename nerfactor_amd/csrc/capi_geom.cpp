@@ -1,102 +1,13 @@
 // capi_geom.cpp — C-ABI entry points of the geometry-extraction kernels (include/nfx.h): density only, and density
-// with its spatial gradient (geometry_from_nerf.py:249-350).
+// with its spatial gradient (geometry_from_nerf.py:249-350).  Their blob (nfx_nerf_pack_geom_weights) is laid out in
+// pack_nets.cpp.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <string.h>
-
-#include <vector>
 
 #include "capi_common.hpp"
-#include "nerf_geom_layout.hpp"
 #include "nerf_points.hpp"
-#include "pack.hpp"
 
 extern "C" {
-size_t nfx_nerf_geom_packed_bytes(int prec) {
-    using namespace nfx::nerf;
-    if (prec == NFX_PREC_BF16) return (size_t)kGeoBlobBytes;
-    if (prec == NFX_PREC_FP32) return 2 * (size_t)kGeoWeightBytes + kGeoFloats * sizeof(float);   // [hi | lo | floats]
-    return 0;
-}
-}  // extern "C"
-
-// The bf16 fragments of nerf_geom_layout.hpp's chunk sequence at w0 and its kGeoFloats floats at fl.
-static int pack_geom_half(const float* const kernels[12], const float* const biases[12], uint8_t* w0, float* fl) {
-    using namespace nfx;
-    using namespace nfx::pack;
-    std::vector<uint8_t> fwd(nfx_nerf_packed_bytes(NFX_PREC_BF16));
-    int rc = nfx_nerf_pack_weights(kernels, biases, NFX_PREC_BF16, fwd.data(), fwd.size());
-    if (rc) return rc;
-    // forward: encoder chunks 0..63 and the sigma tile (chunk 72 = 9th tile of the fused [bottleneck | sigma_out])
-    const size_t enc_bytes = (size_t)nerf::chunk_frag_offset(64) * 1024;
-    memcpy(w0, fwd.data(), enc_bytes);
-    memcpy(w0 + enc_bytes, fwd.data() + (size_t)nerf::chunk_frag_offset(72) * 1024, 16 * 1024);
-    uint8_t* w = w0 + enc_bytes + 16 * 1024;
-    std::vector<float> sink(256);
-    const Seg hid256{kHidden, 256, 0, nullptr};
-    auto hidden_t = [](const float* k) {  // W[:256, :256]^T
-        std::vector<float> t((size_t)256 * 256);
-        for (int r = 0; r < 256; ++r)
-            for (int c = 0; c < 256; ++c) t[(size_t)c * 256 + r] = k[(size_t)r * 256 + c];
-        return t;
-    };
-    // input-gradient product: kernel'[k][f'] = W[row0 + posenc_row(slot f')][k], f' = F(s,h,j) of the slot, so the
-    // C/D lane map of the output tile IS the posenc slot layout of mlp_engine.hpp:posenc<10>
-    auto input_t = [](const float* k, int row0) {
-        std::vector<float> t((size_t)256 * 64, 0.f);
-        const Seg pe{kPosEnc, 10, 0, nullptr};
-        for (int s = 0; s < 4; ++s)
-            for (int h = 0; h < 2; ++h)
-                for (int j = 0; j < 8; ++j) {
-                    const int src = seg_row(pe, s, h, j);
-                    if (src < 0) continue;
-                    const int fp = 32 * (s >> 1) + 16 * (s & 1) + (j & 3) + 8 * (j >> 2) + 4 * h;
-                    for (int kk = 0; kk < 256; ++kk) t[(size_t)kk * 64 + fp] = k[(size_t)(row0 + src) * 256 + kk];
-                }
-        return t;
-    };
-    auto dgrad = [&](int l) {
-        std::vector<float> t = hidden_t(kernels[l]);
-        w += pack_layer_bf16({hid256}, {{t.data(), nullptr, 256}}, 8, 16, w, sink.data());
-    };
-    auto igrad = [&](int l, int row0) {
-        std::vector<float> t = input_t(kernels[l], row0);
-        w += pack_layer_bf16({hid256}, {{t.data(), nullptr, 64}}, 2, 16, w, sink.data());
-    };
-    dgrad(7);
-    dgrad(6);
-    igrad(5, 256);
-    for (int l = 5; l >= 1; --l) dgrad(l);
-    igrad(0, 0);
-    if (w != w0 + nerf::kGeoWeightBytes) return nfx_fail(NFX_EINVAL, "nfx_nerf_pack_geom_weights: layout mismatch");
-    const float* fb = reinterpret_cast<const float*>(fwd.data() + nerf::kWeightBytes);
-    memcpy(fl, fb + nerf::kBiasL0, 8 * 256 * 4);
-    memcpy(fl + nerf::kGeoBiasSig, fb + nerf::kBiasBott + 256, 32 * 4);
-    // sigma_out kernel in fp32: the bf16 kernel rounds it to bf16 when it forms dZ7, as the forward's packed copy is;
-    // the fp32-class kernel splits it into a hi / lo pair
-    memcpy(fl + nerf::kGeoWSig, kernels[8], 256 * 4);
-    return NFX_OK;
-}
-
-extern "C" {
-int nfx_nerf_pack_geom_weights(const float* const kernels[12], const float* const biases[12], int prec, void* blob,
-                               size_t blob_bytes) {
-    using namespace nfx;
-    REQUIRE(kernels && biases && blob, "nfx_nerf_pack_geom_weights: null argument");
-    for (int i = 0; i < 12; ++i) REQUIRE(kernels[i] && biases[i], "nfx_nerf_pack_geom_weights: layer %d null", i);
-    REQUIRE(prec == NFX_PREC_BF16 || prec == NFX_PREC_FP32, "nfx_nerf_pack_geom_weights: bad prec %d", prec);
-    REQUIRE(blob_bytes >= nfx_nerf_geom_packed_bytes(prec), "nfx_nerf_pack_geom_weights: blob too small (%zu < %zu)",
-            blob_bytes, nfx_nerf_geom_packed_bytes(prec));
-    uint8_t* w0 = static_cast<uint8_t*>(blob);
-    if (prec == NFX_PREC_BF16) return pack_geom_half(kernels, biases, w0, reinterpret_cast<float*>(w0 + nerf::kGeoWeightBytes));
-    // NFX_PREC_FP32 (nerf_geom_x3.hip): the chunk sequence of hi = bf16(W), then of lo = bf16(W - hi), then the floats
-    const pack::LoKernels lo = pack::lo_kernels(kernels, pack::kNerfShapes, 12);
-    std::vector<float> sink(nerf::kGeoFloats);
-    int rc = pack_geom_half(kernels, biases, w0, reinterpret_cast<float*>(w0 + 2 * (size_t)nerf::kGeoWeightBytes));
-    if (rc) return rc;
-    return pack_geom_half(lo.ptr.data(), biases, w0 + nerf::kGeoWeightBytes, sink.data());
-}
-
 // The three point descriptions of nerf_points.hpp.  A listed launch has n_pts = the list's capacity, every sample.
 static nfx::geo::Points every_sample(const float* rayo, const float* rayd, const float* z, int64_t n_rays, int n_samples) {
     return {rayo, rayd, z, (long long)n_rays * n_samples, n_samples, nullptr, nullptr, 1, 0};

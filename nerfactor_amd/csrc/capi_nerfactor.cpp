@@ -1,124 +1,15 @@
-// capi_nerfactor.cpp — C-ABI entry points of the NeRFactor surface-shading stage (include/nfx.h).
+// capi_nerfactor.cpp — C-ABI entry points of the NeRFactor surface-shading stage (include/nfx.h).  Its networks' blobs
+// (nfx_mlp128_pack_weights) are laid out in pack_nets.cpp.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
-
-#include <vector>
 
 #include "capi_common.hpp"
 #include "brdf_rows_geom.hpp"
 #include "mlp128_layout.hpp"
-#include "pack.hpp"
 
 extern "C" {
-// ------------------------------------------------------------------------------ packing
-size_t nfx_mlp128_packed_bytes(int in_kind, int z_dim, int out_dim, int prec) {
-    using namespace nfx::m128;
-    if (out_dim < 1 || out_dim > 8) return 0;
-    if (prec == NFX_PREC_FP32) {   // mlp128_x3.hip: [hi fragments | lo fragments | biases]
-        if (in_kind != NFX_IN_XYZ && in_kind != NFX_IN_XYZ_LDIR &&
-            !(in_kind == NFX_IN_Z_RUSINK && z_dim >= 1 && z_dim <= kMaxZDim))
-            return 0;
-        return 2 * (size_t)nfx_mlp128_x3_weight_bytes(in_kind) + kMainBiasFloats * sizeof(float);
-    }
-    if (prec != NFX_PREC_BF16) return 0;
-    if (in_kind == NFX_IN_XYZ) return kMainBytes;
-    if (in_kind == NFX_IN_XYZ_LDIR) return (size_t)kPreBytes + kMainBytes;
-    if (in_kind == NFX_IN_Z_RUSINK && z_dim >= 1 && z_dim <= kMaxZDim) return kMainBytes;
-    return 0;
-}
-
-// One half (hi or lo) of the NFX_PREC_FP32 blob: the plain five layers, the light-visibility input NOT folded.
-static int pack_m128_x3_half(const float* const kernels[5], const float* const biases[5], int in_kind, int z_dim,
-                             int out_dim, uint8_t* w, float* b) {
-    using namespace nfx::pack;
-    const uint8_t* w0 = w;
-    const Seg hid{kHidden, 128, 0, nullptr};
-    int slots[32];
-    nfx::m128::brdf_input_slots(z_dim, slots);
-    std::vector<Seg> in0, in3{hid};
-    int p0 = 4, p3 = 12;
-    if (in_kind == NFX_IN_Z_RUSINK) {
-        in0 = {Seg{kRaw, 2, 0, slots}};
-        in3.push_back(Seg{kRaw, 2, 128, slots});
-    } else {
-        in0 = {Seg{kPosEnc, 10, 0, nullptr}};
-        in3.push_back(Seg{kPosEnc, 10, 128, nullptr});
-        if (in_kind == NFX_IN_XYZ_LDIR) {
-            in0.push_back(Seg{kPosEnc, 4, 63, nullptr});
-            in3.push_back(Seg{kPosEnc, 4, 128 + 63, nullptr});
-            p0 = 8;
-            p3 = 16;
-        }
-    }
-    w += pack_layer_bf16(in0, {{kernels[0], biases[0], 128}}, 4, p0, w, b);
-    w += pack_layer_bf16({hid}, {{kernels[1], biases[1], 128}}, 4, 8, w, b + 128);
-    w += pack_layer_bf16({hid}, {{kernels[2], biases[2], 128}}, 4, 8, w, b + 256);
-    w += pack_layer_bf16(in3, {{kernels[3], biases[3], 128}}, 4, p3, w, b + 384);
-    w += pack_layer_bf16({hid}, {{kernels[4], biases[4], out_dim}}, 1, 8, w, b + 512);
-    return w - w0 == nfx_mlp128_x3_weight_bytes(in_kind) ? 0 : 1;
-}
-
-int nfx_mlp128_pack_weights(const float* const kernels[5], const float* const biases[5], int in_kind,
-                            int z_dim, int out_dim, int prec, void* blob, size_t blob_bytes) {
-    using namespace nfx::m128;
-    using namespace nfx::pack;
-    REQUIRE(kernels && biases && blob, "nfx_mlp128_pack_weights: null argument");
-    for (int i = 0; i < 5; ++i) REQUIRE(kernels[i] && biases[i], "nfx_mlp128_pack_weights: layer %d null", i);
-    REQUIRE(prec == NFX_PREC_BF16 || prec == NFX_PREC_FP32, "nfx_mlp128_pack_weights: bad prec %d", prec);
-    const size_t need = nfx_mlp128_packed_bytes(in_kind, z_dim, out_dim, prec);
-    REQUIRE(need != 0, "nfx_mlp128_pack_weights: unsupported configuration (in_kind %d, z_dim %d, out_dim %d)",
-            in_kind, z_dim, out_dim);
-    REQUIRE(blob_bytes >= need, "nfx_mlp128_pack_weights: blob too small (%zu < %zu)", blob_bytes, need);
-    const int in_dims = in_dims_of(in_kind, z_dim);
-    uint8_t* w = static_cast<uint8_t*>(blob);
-    if (prec == NFX_PREC_FP32) {
-        const Shape shapes[5] = {{in_dims, 128}, {128, 128}, {128, 128}, {128 + in_dims, 128}, {128, out_dim}};
-        const LoKernels lo = lo_kernels(kernels, shapes, 5);
-        const size_t wb = nfx_mlp128_x3_weight_bytes(in_kind);
-        std::vector<float> sink(kMainBiasFloats);
-        memset(w, 0, need);
-        if (pack_m128_x3_half(kernels, biases, in_kind, z_dim, out_dim, w, reinterpret_cast<float*>(w + 2 * wb)) ||
-            pack_m128_x3_half(lo.ptr.data(), biases, in_kind, z_dim, out_dim, w + wb, sink.data()))
-            return nfx_fail(NFX_EINVAL, "nfx_mlp128_pack_weights: layout mismatch (fp32)");
-        return NFX_OK;
-    }
-    const Seg hid{kHidden, 128, 0, nullptr};
-    int slots[32];
-    nfx::m128::brdf_input_slots(z_dim, slots);
-    if (in_kind == NFX_IN_XYZ_LDIR) {
-        float* pb = reinterpret_cast<float*>(w + kPreWeightBytes);
-        w += pack_layer_bf16({Seg{kPosEnc, 10, 0, nullptr}}, {{kernels[0], biases[0], 128}}, 4, 4, w, pb);
-        w += pack_layer_bf16({Seg{kPosEnc, 10, 128, nullptr}}, {{kernels[3], biases[3], 128}}, 4, 4, w,
-                             pb + 128);
-        w += kPreBiasFloats * 4;
-    }
-    uint8_t* main0 = w;
-    float* b = reinterpret_cast<float*>(main0 + kMainWeightBytes);
-    Seg in0, in3;
-    const float *bias0 = biases[0], *bias3 = biases[3];
-    if (in_kind == NFX_IN_XYZ) {
-        in0 = Seg{kPosEnc, 10, 0, nullptr};
-        in3 = Seg{kPosEnc, 10, 128, nullptr};
-    } else if (in_kind == NFX_IN_XYZ_LDIR) {
-        in0 = Seg{kPosEnc, 4, 63, nullptr};      // rows 63..89 = posenc4(ldir)
-        in3 = Seg{kPosEnc, 4, 128 + 63, nullptr};
-        bias0 = bias3 = nullptr;                 // folded into the per-point pre-activation
-    } else {
-        in0 = Seg{kRaw, 2, 0, slots};
-        in3 = Seg{kRaw, 2, 128, slots};
-    }
-    w += pack_layer_bf16({in0}, {{kernels[0], bias0, 128}}, 4, 4, w, b);
-    w += pack_layer_bf16({hid}, {{kernels[1], biases[1], 128}}, 4, 8, w, b + 128);
-    w += pack_layer_bf16({hid}, {{kernels[2], biases[2], 128}}, 4, 8, w, b + 256);
-    w += pack_layer_bf16({hid, in3}, {{kernels[3], bias3, 128}}, 4, 12, w, b + 384);
-    w += pack_layer_bf16({hid}, {{kernels[4], biases[4], out_dim}}, 1, 8, w, b + 512);
-    if (w != main0 + kMainWeightBytes) return nfx_fail(NFX_EINVAL, "nfx_mlp128_pack_weights: layout mismatch");
-    return NFX_OK;
-}
-
 // -------------------------------------------------------------------------------- MLPs
 int nfx_mlp128_xyz_fwd(const float* xyz, int64_t n, float xyz_scale, const void* blob, int out_dim,
                        int out_act, float post_scale, float post_bias, int prec, float* out, void* stream) {

@@ -1,72 +1,15 @@
-// capi_train.cpp — C-ABI entry points of the training-side kernels (include/nfx.h).
+// capi_train.cpp — C-ABI entry points of the training-side kernels (include/nfx.h).  The training blobs
+// (nfx_*_pack_train_weights) are laid out in pack_nets.cpp.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <string.h>
 
 #include <vector>
 
 #include "capi_common.hpp"
 #include "mlp128_layout.hpp"
 #include "nerf_train_layout.hpp"
-#include "pack.hpp"
 
 extern "C" {
-static bool kind_ok(int k) { return k == NFX_IN_XYZ || k == NFX_IN_XYZ_LDIR; }
-
-size_t nfx_mlp128_train_packed_bytes(int in_kind) {
-    return kind_ok(in_kind) ? (size_t)nfx_mlp128_train_blob_bytes(in_kind) : 0;
-}
-
-int nfx_mlp128_pack_train_weights(const float* const kernels[5], const float* const biases[5], int in_kind,
-                                  int out_dim, int prec, void* blob, size_t blob_bytes) {
-    using namespace nfx::pack;
-    REQUIRE(kernels && biases && blob, "nfx_mlp128_pack_train_weights: null argument");
-    for (int i = 0; i < 5; ++i) REQUIRE(kernels[i] && biases[i], "nfx_mlp128_pack_train_weights: layer %d null", i);
-    REQUIRE(kind_ok(in_kind), "nfx_mlp128_pack_train_weights: in_kind %d has no backward", in_kind);
-    REQUIRE(out_dim >= 1 && out_dim <= 8, "nfx_mlp128_pack_train_weights: out_dim %d not in [1, 8]", out_dim);
-    if (prec != NFX_PREC_BF16) return nfx_fail(NFX_ENOSUP, "nfx_mlp128_pack_train_weights: only bf16 is built");
-    const size_t need = nfx_mlp128_train_packed_bytes(in_kind);
-    REQUIRE(blob_bytes >= need, "nfx_mlp128_pack_train_weights: blob too small (%zu < %zu)", blob_bytes, need);
-    const bool lv = in_kind == NFX_IN_XYZ_LDIR;
-    const int p0 = lv ? 8 : 4, p3 = lv ? 16 : 12;
-    uint8_t* w = static_cast<uint8_t*>(blob);
-    float* b = reinterpret_cast<float*>(w + need - nfx::m128::kMainBiasFloats * 4);
-    const Seg hid{kHidden, 128, 0, nullptr};
-    std::vector<Seg> in0{Seg{kPosEnc, 10, 0, nullptr}}, in3{hid, Seg{kPosEnc, 10, 128, nullptr}};
-    if (lv) {
-        in0.push_back(Seg{kPosEnc, 4, 63, nullptr});
-        in3.push_back(Seg{kPosEnc, 4, 128 + 63, nullptr});
-    }
-    // ---- forward fragments (same dataflow as the inference kernels, un-folded input)
-    w += pack_layer_bf16(in0, {{kernels[0], biases[0], 128}}, 4, p0, w, b);
-    w += pack_layer_bf16({hid}, {{kernels[1], biases[1], 128}}, 4, 8, w, b + 128);
-    w += pack_layer_bf16({hid}, {{kernels[2], biases[2], 128}}, 4, 8, w, b + 256);
-    w += pack_layer_bf16(in3, {{kernels[3], biases[3], 128}}, 4, p3, w, b + 384);
-    w += pack_layer_bf16({hid}, {{kernels[4], biases[4], out_dim}}, 1, 8, w, b + 512);
-    // ---- dgrad fragments: layer l backward = a Dense whose Keras kernel is W_l^T ([out, in])
-    std::vector<float> scratch_bias(128, 0.f), bias_sink(128 * 4);
-    auto transposed = [&](const float* k, int rows_used, int cols, int pad_rows) {
-        std::vector<float> t((size_t)pad_rows * rows_used, 0.f);  // [cols(pad) , rows_used]
-        for (int r = 0; r < rows_used; ++r)
-            for (int c = 0; c < cols; ++c) t[(size_t)c * rows_used + r] = k[(size_t)r * cols + c];
-        return t;
-    };
-    {   // through the out layer: dH3[128] = Wo[128, out] dZo[out]; 16 padded gradient slots
-        std::vector<float> t = transposed(kernels[4], 128, out_dim, 16);
-        w += pack_layer_bf16({Seg{kHidden, 16, 0, nullptr}}, {{t.data(), nullptr, 128}}, 4, 4, w, bias_sink.data());
-    }
-    {   // through L3: only the h2 rows (first 128) carry a gradient that is needed
-        std::vector<float> t = transposed(kernels[3], 128, 128, 128);
-        w += pack_layer_bf16({hid}, {{t.data(), nullptr, 128}}, 4, 8, w, bias_sink.data());
-    }
-    for (int l = 2; l >= 1; --l) {
-        std::vector<float> t = transposed(kernels[l], 128, 128, 128);
-        w += pack_layer_bf16({hid}, {{t.data(), nullptr, 128}}, 4, 8, w, bias_sink.data());
-    }
-    if (w != reinterpret_cast<uint8_t*>(b)) return nfx_fail(NFX_EINVAL, "nfx_mlp128_pack_train_weights: layout mismatch");
-    return NFX_OK;
-}
-
 static long long ld_for(int in_kind, int64_t n, int n_lights) {
     const long long rows = in_kind == NFX_IN_XYZ ? n : n * (long long)n_lights;
     return (rows + 127) / 128 * 128;
@@ -87,7 +30,7 @@ static size_t mlp128_feat_bytes(int in_kind, int64_t n, int n_lights) {
 static bool fused_wgrad() { return nfx_option_int("wgrad_fused", 1) != 0; }
 
 size_t nfx_mlp128_bwd_workspace_bytes(int in_kind, int64_t n, int n_lights) {
-    if (!kind_ok(in_kind) || n <= 0) return 0;
+    if (!m128_has_backward(in_kind) || n <= 0) return 0;
     if (fused_wgrad())
         return nfx_mlp128_fused_partial_floats(in_kind, nfx_mlp128_fused_grid(in_kind, n, n_lights,
                                                                             nfx_option_int("m128_blocks", 256))) * sizeof(float);
@@ -102,7 +45,7 @@ int nfx_mlp128_bwd(int in_kind, const float* xyz, const float* xyz_dir, int64_t 
                    const float* lxyz, int n_lights, const void* blob, int out_dim, int out_act,
                    float post_scale, const float* dout, void* workspace, size_t workspace_bytes,
                    float* const dkernels[5], float* const dbiases[5], int prec, void* stream) {
-    REQUIRE(kind_ok(in_kind), "nfx_mlp128_bwd: in_kind %d has no backward", in_kind);
+    REQUIRE(m128_has_backward(in_kind), "nfx_mlp128_bwd: in_kind %d has no backward", in_kind);
     REQUIRE(n >= 0, "nfx_mlp128_bwd: n < 0");
     REQUIRE(out_dim >= 1 && out_dim <= 8 && out_act >= 0 && out_act <= 3, "nfx_mlp128_bwd: bad out_dim/act");
     if (prec != NFX_PREC_BF16) return nfx_fail(NFX_ENOSUP, "nfx_mlp128_bwd: only bf16 is built");
@@ -167,7 +110,7 @@ int nfx_mlp128_bwd_heads(int in_kind, const float* xyz, const float* xyz_dir, in
         }
         return NFX_OK;
     }
-    REQUIRE(kind_ok(in_kind), "nfx_mlp128_bwd_heads: in_kind %d has no backward", in_kind);
+    REQUIRE(m128_has_backward(in_kind), "nfx_mlp128_bwd_heads: in_kind %d has no backward", in_kind);
     REQUIRE(n >= 0, "nfx_mlp128_bwd_heads: n < 0");
     if (prec != NFX_PREC_BF16) return nfx_fail(NFX_ENOSUP, "nfx_mlp128_bwd_heads: only bf16 is built");
     if (in_kind == NFX_IN_XYZ_LDIR) REQUIRE(n_lights > 0 && lxyz, "nfx_mlp128_bwd_heads: light positions required for NFX_IN_XYZ_LDIR");
@@ -193,59 +136,6 @@ int nfx_mlp128_bwd_heads(int in_kind, const float* xyz, const float* xyz_dir, in
 }
 
 // ------------------------------------------------------------------------------------ NeRF MLP backward
-size_t nfx_nerf_train_packed_bytes(int prec) { return prec == NFX_PREC_BF16 ? (size_t)nfx::nerf::kTrainBlobBytes : 0; }
-
-int nfx_nerf_pack_train_weights(const float* const kernels[12], const float* const biases[12], int prec, void* blob,
-                                size_t blob_bytes) {
-    using namespace nfx;
-    using namespace nfx::pack;
-    REQUIRE(kernels && biases && blob, "nfx_nerf_pack_train_weights: null argument");
-    for (int i = 0; i < 12; ++i) REQUIRE(kernels[i] && biases[i], "nfx_nerf_pack_train_weights: layer %d null", i);
-    if (prec != NFX_PREC_BF16) return nfx_fail(NFX_ENOSUP, "nfx_nerf_pack_train_weights: only bf16 is built");
-    REQUIRE(blob_bytes >= (size_t)nerf::kTrainBlobBytes, "nfx_nerf_pack_train_weights: blob too small (%zu < %d)",
-            blob_bytes, nerf::kTrainBlobBytes);
-    uint8_t* w0 = static_cast<uint8_t*>(blob);
-    // forward fragments + biases: the inference packer's layout, biases moved behind the dgrad fragments
-    std::vector<uint8_t> fwd(nfx_nerf_packed_bytes(prec));
-    int rc = nfx_nerf_pack_weights(kernels, biases, prec, fwd.data(), fwd.size());
-    if (rc) return rc;
-    memcpy(w0, fwd.data(), nerf::kWeightBytes);
-    memcpy(w0 + nerf::kTrainWeightBytes, fwd.data() + nerf::kWeightBytes, (size_t)nerf::kBiasFloats * 4);
-    uint8_t* w = w0 + nerf::kWeightBytes;
-    std::vector<float> sink(256);
-    // W[r0 : r0 + n_in_used, :cols]^T as a Keras kernel [pad_in' = cols padded, out' = n_rows]
-    auto transposed = [](const float* k, int row0, int n_rows, int cols, int pad_cols) {
-        std::vector<float> t((size_t)pad_cols * n_rows, 0.f);
-        for (int r = 0; r < n_rows; ++r)
-            for (int c = 0; c < cols; ++c) t[(size_t)c * n_rows + r] = k[(size_t)(row0 + r) * cols + c];
-        return t;
-    };
-    const Seg hid256{kHidden, 256, 0, nullptr}, hid128{kHidden, 128, 0, nullptr}, hid16{kHidden, 16, 0, nullptr};
-    {   // D1: dR0[128] = Wrgb1[128, 3] dZrgb[3]
-        std::vector<float> t = transposed(kernels[11], 0, 128, 3, 16);
-        w += pack_layer_bf16({hid16}, {{t.data(), nullptr, 128}}, 4, 4, w, sink.data());
-    }
-    {   // D2: dBott[256] = Wrgb0[:256, 128] dZr0[128]
-        std::vector<float> t = transposed(kernels[10], 0, 256, 128, 128);
-        w += pack_layer_bf16({hid128}, {{t.data(), nullptr, 256}}, 8, 8, w, sink.data());
-    }
-    {   // D3: dA7[256] = Wbott[256, 256] dZbott[256] + Wsigma[256, 1] dZsigma  (input rows: 256 + 16 slots)
-        std::vector<float> t((size_t)(256 + 16) * 256, 0.f);
-        for (int r = 0; r < 256; ++r) {
-            for (int c = 0; c < 256; ++c) t[(size_t)c * 256 + r] = kernels[9][(size_t)r * 256 + c];
-            t[(size_t)256 * 256 + r] = kernels[8][r];
-        }
-        const Seg sig{kHidden, 16, 256, nullptr};
-        w += pack_layer_bf16({hid256, sig}, {{t.data(), nullptr, 256}}, 8, 20, w, sink.data());
-    }
-    for (int l = 7; l >= 1; --l) {  // dA_{l-1}[256] = W_l[:256, 256] dZ_l[256]   (enc[5]: the y rows of [y, posenc])
-        std::vector<float> t = transposed(kernels[l], 0, 256, 256, 256);
-        w += pack_layer_bf16({hid256}, {{t.data(), nullptr, 256}}, 8, 16, w, sink.data());
-    }
-    if (w != w0 + nerf::kTrainWeightBytes) return nfx_fail(NFX_EINVAL, "nfx_nerf_pack_train_weights: layout mismatch");
-    return NFX_OK;
-}
-
 static long long nerf_ld(long long n_pts) { return (n_pts + 255) / 256 * 256; }   // whole 256-row tiles (nerf_bwd.hip)
 
 static const int kNerfWgradDims[14][2] = {{63, 256}, {256, 256}, {256, 256}, {256, 256}, {256, 256}, {256, 256},
@@ -338,68 +228,6 @@ int nfx_pack_gather(const float* src, const int32_t* map, int64_t n_words, void*
     if (!ALIGNED(blob, 16) || !ALIGNED(map, 8))
         return nfx_fail(NFX_EALIGN, "nfx_pack_gather: blob must be 16-byte and map 8-byte aligned");
     return nfx_hip_result(nfx_launch_pack_gather(src, map, n_words, blob, (hipStream_t)stream), "pack_gather");
-}
-
-size_t nfx_brdf_train_packed_bytes(void) { return (size_t)nfx_brdf_train_blob_bytes(); }
-
-int nfx_brdf_pack_train_weights(const float* const kernels[5], const float* const biases[5], int z_dim, int prec,
-                                void* blob, size_t blob_bytes) {
-    using namespace nfx::pack;
-    REQUIRE(kernels && biases && blob, "nfx_brdf_pack_train_weights: null argument");
-    for (int i = 0; i < 5; ++i) REQUIRE(kernels[i] && biases[i], "nfx_brdf_pack_train_weights: layer %d null", i);
-    REQUIRE(z_dim >= 1 && z_dim <= nfx::m128::kMaxZDim, "nfx_brdf_pack_train_weights: z_dim %d unsupported", z_dim);
-    if (prec != NFX_PREC_BF16) return nfx_fail(NFX_ENOSUP, "nfx_brdf_pack_train_weights: only bf16 is built");
-    const size_t need = nfx_brdf_train_packed_bytes();
-    REQUIRE(blob_bytes >= need, "nfx_brdf_pack_train_weights: blob too small (%zu < %zu)", blob_bytes, need);
-    int slots[32];
-    nfx::m128::brdf_input_slots(z_dim, slots);
-    uint8_t* w = static_cast<uint8_t*>(blob);
-    float* b = reinterpret_cast<float*>(w + need - nfx::m128::kMainBiasFloats * 4);
-    const Seg hid{kHidden, 128, 0, nullptr};
-    const Seg in0{kRaw, 2, 0, slots}, in3{kRaw, 2, 128, slots};
-    w += pack_layer_bf16({in0}, {{kernels[0], biases[0], 128}}, 4, 4, w, b);
-    w += pack_layer_bf16({hid}, {{kernels[1], biases[1], 128}}, 4, 8, w, b + 128);
-    w += pack_layer_bf16({hid}, {{kernels[2], biases[2], 128}}, 4, 8, w, b + 256);
-    w += pack_layer_bf16({hid, in3}, {{kernels[3], biases[3], 128}}, 4, 12, w, b + 384);
-    w += pack_layer_bf16({hid}, {{kernels[4], biases[4], 1}}, 1, 8, w, b + 512);
-    std::vector<float> sink(128 * 4);
-    auto hidden_t = [&](const float* k, int cols, int pad_rows) {  // W[:128, :cols]^T as [pad_rows, 128]
-        std::vector<float> t((size_t)pad_rows * 128, 0.f);
-        for (int r = 0; r < 128; ++r)
-            for (int c = 0; c < cols; ++c) t[(size_t)c * 128 + r] = k[(size_t)r * cols + c];
-        return t;
-    };
-    // input-gradient products: kernel'[k][f'] = W[row0 + input_row(slot f')][k], f' = F(s,h,j) of the slot
-    auto input_t = [&](const float* k, int row0) {
-        std::vector<float> t((size_t)128 * 32, 0.f);
-        for (int s = 0; s < 2; ++s)
-            for (int h = 0; h < 2; ++h)
-                for (int j = 0; j < 8; ++j) {
-                    const int src = slots[(s * 2 + h) * 8 + j];
-                    if (src < 0) continue;
-                    const int fp = 16 * s + (j & 3) + 8 * (j >> 2) + 4 * h;
-                    for (int kk = 0; kk < 128; ++kk) t[(size_t)kk * 32 + fp] = k[(size_t)(row0 + src) * 128 + kk];
-                }
-        return t;
-    };
-    {
-        std::vector<float> t = hidden_t(kernels[4], 1, 16);           // through the out layer
-        w += pack_layer_bf16({Seg{kHidden, 16, 0, nullptr}}, {{t.data(), nullptr, 128}}, 4, 4, w, sink.data());
-    }
-    {
-        std::vector<float> t = input_t(kernels[3], 128);              // W3[128:, :] dZ3 -> input slots
-        w += pack_layer_bf16({hid}, {{t.data(), nullptr, 32}}, 1, 8, w, sink.data());
-    }
-    for (int l = 3; l >= 1; --l) {                                    // hidden-to-hidden dgrads
-        std::vector<float> t = hidden_t(kernels[l], 128, 128);
-        w += pack_layer_bf16({hid}, {{t.data(), nullptr, 128}}, 4, 8, w, sink.data());
-    }
-    {
-        std::vector<float> t = input_t(kernels[0], 0);                // W0 dZ0 -> input slots
-        w += pack_layer_bf16({hid}, {{t.data(), nullptr, 32}}, 1, 8, w, sink.data());
-    }
-    if (w != reinterpret_cast<uint8_t*>(b)) return nfx_fail(NFX_EINVAL, "nfx_brdf_pack_train_weights: layout mismatch");
-    return NFX_OK;
 }
 
 size_t nfx_brdf_spec_bwd_workspace_bytes(int z_dim, int64_t n) {

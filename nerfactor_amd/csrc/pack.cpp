@@ -35,6 +35,16 @@ LoKernels lo_kernels(const float* const* kernels, const Shape* shapes, int n) {
     return lo;
 }
 
+int pack_hi_lo(const float* const* kernels, const Shape* shapes, int n, size_t weight_bytes, int n_floats, uint8_t* blob,
+               const PackHalf& pack_half) {
+    const LoKernels lo = lo_kernels(kernels, shapes, n);
+    std::vector<float> sink(n_floats);
+    if (int rc = pack_half(kernels, blob, reinterpret_cast<float*>(blob + 2 * weight_bytes))) return rc;
+    return pack_half(lo.ptr.data(), blob + weight_bytes, sink.data());
+}
+
+int hidden_feature(int s, int h, int j) { return 32 * (s >> 1) + 16 * (s & 1) + (j & 3) + 8 * (j >> 2) + 4 * h; }
+
 int seg_ksteps(const Seg& s) {
     switch (s.kind) {
         case kHidden: return s.n / 16;
@@ -44,9 +54,7 @@ int seg_ksteps(const Seg& s) {
 }
 
 int seg_row(const Seg& seg, int s, int h, int j) {
-    if (seg.kind == kHidden) {
-        return seg.row0 + 32 * (s >> 1) + 16 * (s & 1) + (j & 3) + 8 * (j >> 2) + 4 * h;
-    }
+    if (seg.kind == kHidden) return seg.row0 + hidden_feature(s, h, j);
     if (seg.kind == kPosEnc) {
         const int L = seg.n, q = 8 * s + j;
         int e;
@@ -107,6 +115,41 @@ size_t pack_layer_bf16(const std::vector<Seg>& segs, const std::vector<Src>& src
         }
     }
     return (size_t)n_tiles * chunk_elems * 2;
+}
+
+size_t pack_m128_ladder(const std::vector<Seg>& in0, const std::vector<Seg>& in3, int p0, int p3, const float* const kernels[5],
+                        const float* const biases[5], int out_dim, uint8_t* w, float* b) {
+    const uint8_t* w0 = w;
+    const Seg hid{kHidden, 128, 0, nullptr};
+    std::vector<Seg> hid_in3{hid};
+    hid_in3.insert(hid_in3.end(), in3.begin(), in3.end());
+    w += pack_layer_bf16(in0, {{kernels[0], biases[0], 128}}, 4, p0, w, b);
+    w += pack_layer_bf16({hid}, {{kernels[1], biases[1], 128}}, 4, 8, w, b + 128);
+    w += pack_layer_bf16({hid}, {{kernels[2], biases[2], 128}}, 4, 8, w, b + 256);
+    w += pack_layer_bf16(hid_in3, {{kernels[3], biases[3], 128}}, 4, p3, w, b + 384);
+    w += pack_layer_bf16({hid}, {{kernels[4], biases[4], out_dim}}, 1, 8, w, b + 512);
+    return w - w0;
+}
+
+std::vector<float> transposed(const float* kernel, int row0, int n_rows, int cols, int pad_cols) {
+    std::vector<float> t((size_t)pad_cols * n_rows, 0.f);
+    for (int r = 0; r < n_rows; ++r)
+        for (int c = 0; c < cols; ++c) t[(size_t)c * n_rows + r] = kernel[(size_t)(row0 + r) * cols + c];
+    return t;
+}
+
+std::vector<float> input_grad_kernel(const float* kernel, const Seg& in, int width) {
+    const int ks = seg_ksteps(in), n = 16 * ks;
+    std::vector<float> t((size_t)width * n, 0.f);
+    for (int s = 0; s < ks; ++s)
+        for (int h = 0; h < 2; ++h)
+            for (int j = 0; j < 8; ++j) {
+                const int row = seg_row(in, s, h, j);
+                if (row < 0) continue;
+                const int f = hidden_feature(s, h, j);
+                for (int k = 0; k < width; ++k) t[(size_t)k * n + f] = kernel[(size_t)row * width + k];
+            }
+    return t;
 }
 
 }  // namespace pack

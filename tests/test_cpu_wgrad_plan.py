@@ -10,9 +10,9 @@ import pytest
 
 from tests.conftest import ROOT
 
-NERF = [(63, 256)] + [(256, 256)] * 7 + [(63, 256), (256, 1), (256, 256), (256, 128), (27, 128), (128, 3)]   # capi_train.cpp:296
-W128 = [(90, 128), (128, 128), (128, 128), (128, 128), (90, 128), (128, 8)]                                  # capi_train.cpp:117
-BRDF = [(18, 128), (128, 128), (128, 128), (128, 128), (18, 128), (128, 1)]                                  # capi_train.cpp:517
+NERF = [(63, 256)] + [(256, 256)] * 7 + [(63, 256), (256, 1), (256, 256), (256, 128), (27, 128), (128, 3)]   # capi_train.cpp:kNerfWgradDims
+W128 = [(90, 128), (128, 128), (128, 128), (128, 128), (90, 128), (128, 8)]                                  # capi_train.cpp:mlp128_wgrad_calls
+BRDF = [(18, 128), (128, 128), (128, 128), (128, 128), (18, 128), (128, 1)]                                  # capi_train.cpp:brdf_rows_wgrad_calls
 
 # every multiple of 16 below 4096, then a sample up to ~70 000 that brackets the 16 384-row rule
 ROWS = list(range(16, 4096, 16)) + [4096, 4112, 5008, 8192, 12304, 16368, 16384, 16400, 20000 // 16 * 16, 32768, 40016, 49152,

@@ -192,7 +192,7 @@ def test_the_forms_agree_with_each_other(nfx_lib, cuda, nfx_opt, name):
     nerf_sigma_fwd gives from the geom blob under both sigma_variants, in every layout; the density of the fp32-class kernel is
     nerf_sigma_fwd(..., 'fp32') under both sigma_x3_variants (nerf_mlp_x3_kernel and nerf_sigma_x3_kernel run x3::tile<16, 0, .>
     over the same 16 k-steps of the same activation pairs against the same fragments: the geom blob's sigma tile is a copy of
-    chunk 72 of the full blob, capi_geom.cpp:pack_geom_half; both round the encoder's activations with acc_to_pair<true>); the
+    chunk 72 of the full blob, pack_nets.cpp:pack_geom_fragments; both round the encoder's activations with acc_to_pair<true>); the
     gradient kernels' density is nerf_sigma_fwd's and both sigma_grad_rows settings agree."""
     ps = pc.point_set(name)
     bases = {form: base_of(nfx_opt, cuda, ps, form)[1] for form in ALL_FORMS}

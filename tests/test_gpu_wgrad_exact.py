@@ -50,7 +50,7 @@ class Table:
 
 
 def nerf_table():
-    """The 14 calls of nfx_nerf_mlp_bwd: kNerfWgradDims (capi_train.cpp:296) and the table built at capi_train.cpp:347-355.
+    """The 14 calls of nfx_nerf_mlp_bwd: kNerfWgradDims and the table that function builds (capi_train.cpp).
     {256,256} and {63,256} of layer 5 share zt and write rows 0..255 / 256..318 of one [319, 256] dW, {27,128} writes behind
     {256,128}; both skip-row calls pass db = null."""
     xs = {'pe': 63, 'pv': 27, 'bott': 256, 'r0': 128}
@@ -69,9 +69,9 @@ def nerf_table():
 
 
 def width128_table(name, seed, ind, out_dim):
-    """The six calls of a width-128 backward: mlp128_wgrad_calls (capi_train.cpp:117) and the table at
-    capi_train.cpp:179-186 — ind = 63 | 90, out_dim = 1 .. 8 — and, with ind = z_dim + 15 and out_dim = 1, brdf_rows_wgrad_calls
-    (capi_train.cpp:517) and the table at capi_train.cpp:571-578.  The skip rows go behind layer 3's, without a bias."""
+    """The six calls of a width-128 backward: mlp128_wgrad_calls and the table nfx_mlp128_bwd builds
+    (capi_train.cpp) — ind = 63 | 90, out_dim = 1 .. 8 — and, with ind = z_dim + 15 and out_dim = 1, brdf_rows_wgrad_calls and
+    the table nfx_brdf_rows_bwd builds.  The skip rows go behind layer 3's, without a bias."""
     xs = {'x': ind, 'h0': 128, 'h1': 128, 'h2': 128, 'h3': 128}
     zs = {'dz0': 128, 'dz1': 128, 'dz2': 128, 'dz3': 128, 'dzo': out_dim}
     dws = {'k0': (ind, 128), 'k1': (128, 128), 'k2': (128, 128), 'k3': (128 + ind, 128), 'k4': (128, out_dim)}
