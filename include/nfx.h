@@ -409,6 +409,37 @@ NFX_API size_t nfx_mesh_components_workspace_bytes(int64_t nv, int64_t nf);
 NFX_API int nfx_mesh_components(const int32_t *dev_faces, int64_t nf, int64_t nv, int32_t *dev_label,
                                 void *dev_workspace, size_t workspace_bytes, void *stream);
 
+/* PSNR and SSIM of a batch of image pairs (csrc/image_metrics.hip).
+ *   Images    dev_a, dev_b: [batch, h, w, c] contiguous, uint8 (is_float = 0) or float32 (is_float = 1), c = 1 or 3.
+ *             luma != 0 and c = 3: a pixel's one value is L = (0.2126 r + 0.7152 g) + 0.0722 b and c' = 1 channel is
+ *             scored; otherwise c' = c channels are scored separately.  All arithmetic is fp64 without fused multiply-adds.
+ *   Error     per selected pixel and scored channel e = ((x - y) / max_val)^2; dev_mask (uint8 [batch, h, w], may be
+ *             null) selects the pixels with a non-zero byte.  The mask restricts the error only.
+ *   SSIM      window 11 x 11, VALID; host_weights: the 11 weights g of one axis (host memory, read during the call), the
+ *             window's weights are g[i] g[j], applied as a horizontal then a vertical pass, each sum in ascending tap
+ *             order; c1 = (0.01 max_val)^2, c2 = (0.03 max_val)^2; mx = G*x, my = G*y, sxy = G*(x y), sq = G*(x x + y y);
+ *             v = ((2 mx my + c1) / (mx^2 + my^2 + c1)) ((2 sxy - 2 mx my + c2) / (sq - (mx^2 + my^2) + c2)).
+ *             dev_ssim_map (float64 [batch, h - 10, w - 10, c'], may be null) receives every v.
+ *   Totals    dev_totals: int64 [batch, 8], every word written: words 0-2 the sum of llrint(e 2^40) per scored channel,
+ *             words 3-5 the sum of llrint(v 2^40) per scored channel (0 for a channel not scored), word 6 the number of
+ *             (pixel, channel) errors summed, word 7 non-zero when a value of the image was not finite, or an e above 1
+ *             (the images are outside the declared range): the image's other words then mean nothing.  Integer sums:
+ *             the same bits for every launch shape and on every run, whatever totals and workspace held before.
+ *   Limits    h, w >= 11; h w <= NFX_IMAGE_METRICS_MAX_PIXELS (a channel's total stays below 2^63); 1 <= batch,
+ *             batch c' <= 65535; max_val > 0 and finite; workspace_bytes >= nfx_image_metrics_workspace_bytes(...)
+ *             (0 = arguments outside the limits); refused with their numbers before anything is launched.
+ *   Work      one block per NFX_IMAGE_METRICS_TILE_Y x _X tile of window positions, image and scored channel, through
+ *             LDS; a second launch adds the blocks' integers per image.  No atomics, nothing allocated, no
+ *             synchronisation with the host.                                                                         */
+#define NFX_IMAGE_METRICS_TILE_Y 16
+#define NFX_IMAGE_METRICS_TILE_X 32
+#define NFX_IMAGE_METRICS_MAX_PIXELS (1ll << 22)
+NFX_API size_t nfx_image_metrics_workspace_bytes(int64_t batch, int h, int w, int c, int luma);
+NFX_API int nfx_image_metrics(const void *dev_a, const void *dev_b, int is_float, int64_t batch, int h, int w, int c,
+                              double max_val, int luma, const uint8_t *dev_mask, double *dev_ssim_map,
+                              const double *host_weights, int64_t *dev_totals, void *dev_workspace,
+                              size_t workspace_bytes, void *stream);
+
 /* Rusinkiewicz coordinates (phi_d, theta_h, theta_d), util/geom.py:152-192. a,b [n,3]. */
 NFX_API int nfx_dir2rusink(const float *dev_a, const float *dev_b, int64_t n, float *dev_rusink,
                    void *stream);

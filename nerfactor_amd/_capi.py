@@ -28,6 +28,7 @@ _p = ctypes.c_void_p
 _i = ctypes.c_int
 _i64 = ctypes.c_int64
 _f = ctypes.c_float
+_d = ctypes.c_double
 _sz = ctypes.c_size_t
 _pp = ctypes.POINTER(ctypes.c_void_p)
 
@@ -74,6 +75,8 @@ SIGNATURES = {
     'nfx_isosurface_emit': (_i, [_p, _i, _i, _i, _f, _p, _p, _p, _sz, _i64, _i64, _p, _p, _p]),
     'nfx_mesh_components_workspace_bytes': (_sz, [_i64, _i64]),
     'nfx_mesh_components': (_i, [_p, _i64, _i64, _p, _p, _sz, _p]),
+    'nfx_image_metrics_workspace_bytes': (_sz, [_i64, _i, _i, _i, _i]),
+    'nfx_image_metrics': (_i, [_p, _p, _i, _i64, _i, _i, _i, _d, _i, _p, _p, _p, _p, _p, _sz, _p]),
     'nfx_dir2rusink': (_i, [_p, _p, _i64, _p, _p]),
     'nfx_mlp128_train_packed_bytes': (_sz, [_i]),
     'nfx_mlp128_pack_train_weights': (_i, [_pp, _pp, _i, _i, _i, _p, _sz]),

@@ -55,6 +55,10 @@ int nfx_launch_isosurface_emit(const float* field, int nx, int ny, int nz, float
                                const void* ws, int nv, int nf, float* vertices, int* faces, hipStream_t st);
 // ---- mesh_components.hip (label doubles as the parent array; skipped: word 0 of the workspace)
 int nfx_launch_mesh_components(const int* faces, long long nf, long long nv, int* label, int* skipped, hipStream_t st);
+// ---- image_metrics.hip (cp: channels scored; partial: the workspace, four int64 per block; totals: int64 [batch, 8])
+int nfx_launch_image_metrics(const void* a, const void* b, int is_float, int batch, int h, int w, int c, int cp, double max_val,
+                             const unsigned char* mask, double* ssim_map, const double* host_weights, long long* totals,
+                             long long* partial, hipStream_t st);
 // ---- loss.hip
 int nfx_launch_pair_loss(int bwd, const nfx_loss_term* terms, int n_terms, const float* alpha, float bg, long long n, float* loss,
                          const float* dloss, hipStream_t st);

@@ -26,6 +26,15 @@ from .brdf import Model as BRDFModel
 from .shape import Model as ShapeModel, _mae, _mse
 
 
+def probe_files(envmap_dir):
+    """[(name, path)] of the light probes of test_envmap_dir, in the order the model registers them (novel_probes, and so
+    the order of pred_rgb_probes/%04d.png): the .hdr / .exr / .npy files, sorted by path."""
+    paths = []
+    for ext in ('hdr', 'exr', 'npy'):
+        paths += glob.glob(join(envmap_dir, '*.' + ext)) if envmap_dir else []
+    return [(basename(path)[:-len('.hdr')], path) for path in sorted(paths)]
+
+
 class Model(ShapeModel):
     def __init__(self, config, debug=False):
         # --- BRDF prior (frozen): its own config sits next to its checkpoint
@@ -89,12 +98,8 @@ class Model(ShapeModel):
         # (2) light probes: the .hdr / .exr files of test_envmap_dir (nerfactor.py:88-93), resized to light_res with the
         # reference's antialiased bilinear filter (:169-179); .npy arrays are accepted as an extension
         self.novel_probes = OrderedDict()
-        envmap_dir = cfg.get('DEFAULT', 'test_envmap_dir', fallback='')
-        paths = []
-        for ext in ('hdr', 'exr', 'npy'):
-            paths += glob.glob(join(envmap_dir, '*.' + ext)) if envmap_dir else []
-        for path in sorted(paths):
-            self.add_probe(basename(path)[:-len('.hdr')], self._load_light(path))
+        for name, path in probe_files(cfg.get('DEFAULT', 'test_envmap_dir', fallback='')):
+            self.add_probe(name, self._load_light(path))
         self.embed_light_h = cfg.getint('DEFAULT', 'embed_light_h', fallback=32)
 
     def _load_light(self, path):

@@ -1002,6 +1002,107 @@ def mesh_filter_components(vertices, faces, keep_largest=0, min_faces=0, attrs=(
     return nfx_mesh.filter_by_labels(vertices, faces, label, keep_largest, min_faces, attrs)
 
 
+# ------------------------------------------------------------------------------ image metrics
+IMAGE_METRICS_TILE = (16, 32)                    # (TY, TX): the window positions one block scores (NFX_IMAGE_METRICS_TILE_*)
+IMAGE_METRICS_MAX_PIXELS = 1 << 22               # H * W of one image (NFX_IMAGE_METRICS_MAX_PIXELS)
+IMAGE_METRICS_SCALE = 2 ** 40                    # the fixed point of the integer sums
+
+
+def _ssim_weights():
+    """tf.image.ssim's default window along one axis: 11 taps, sigma 1.5, normalised; Python floats (fp64)."""
+    import math
+    e = [math.exp(-0.5 * (((i - 5) / 1.5) * ((i - 5) / 1.5))) for i in range(11)]
+    s = sum(e)
+    return tuple(x / s for x in e)
+
+
+IMAGE_METRICS_WEIGHTS = _ssim_weights()
+
+
+def image_metrics_finalize(totals, n_map, max_val):
+    """One image's numbers from its eight integers (include/nfx.h): {'mse', 'psnr', 'ssim', 'n_px'}.  Python integers and floats only, so that every step is one correctly rounded fp64 operation:
+    mse = ((se_total / 2^40) / n_px) * max_val^2, psnr = 10 log10(max_val^2 / mse) (inf at mse = 0), ssim = (ssim_total /
+    2^40) / n_map.  NaN for all three when the image's flag is raised, NaN for mse and psnr when no pixel was selected."""
+    import math
+    t = [int(x) for x in totals]
+    se, sm, n_px, flag = t[0] + t[1] + t[2], t[3] + t[4] + t[5], t[6], t[7]
+    nan = float('nan')
+    out = {'mse': nan, 'psnr': nan, 'ssim': nan, 'n_px': n_px}
+    if flag:
+        return out
+    out['ssim'] = float(sm) / float(IMAGE_METRICS_SCALE) / float(n_map)
+    if n_px:
+        peak = float(max_val) * float(max_val)
+        out['mse'] = float(se) / float(IMAGE_METRICS_SCALE) / float(n_px) * peak
+        out['psnr'] = float('inf') if se == 0 else 10. * math.log10(peak / out['mse'])
+    return out
+
+
+def image_metrics(a, b, max_val, luma=True, mask=None, return_map=False, totals=None, ws=None, ssim_map=None):
+    """PSNR and SSIM of B image pairs in one call (nfx_image_metrics).  a, b: contiguous CUDA tensors [B, H, W, C] of the same
+    shape, both uint8 or both float32, C = 1 or 3; max_val: 255 for uint8 content, 1 for unit-range floats.  luma (and C = 3):
+    both images are reduced to L = (0.2126 r + 0.7152 g) + 0.0722 b first (xiuminglib's rgb2lum, as xm.metric.PSNR / SSIM
+    do); otherwise the channels are scored separately and averaged (tf.image.ssim).  mask: uint8 [B, H, W], restricts the
+    squared error (never the SSIM) to its non-zero pixels.
+    -> {'mse', 'psnr', 'ssim': float64 [B] (host tensors; the call reads the B x 8 integer totals back once), 'n_px': int64
+    [B] (pixel, channel) errors summed, 'totals': the int64 [B, 8] words of include/nfx.h on the host, 'ssim_map': float64
+    [B, H - 10, W - 10, C'] on the device with return_map, else None}.  An image holding a NaN or an Inf gives NaN for that
+    image; so does a pair with |a - b| > max_val somewhere (outside the declared range).  `totals`, `ws` (int64) and `ssim_map` may be passed in; what they hold does not matter."""
+    for name, t in (('a', a), ('b', b)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise _capi.NfxError("image_metrics: %s must be a CUDA/ROCm tensor (libnfx has no CPU path)" % name)
+    if a.dtype != b.dtype or a.dtype not in (torch.uint8, torch.float32):
+        raise _capi.NfxError("image_metrics: a is %s and b is %s (both uint8 or both float32)" % (a.dtype, b.dtype))
+    if a.shape != b.shape or a.dim() != 4:
+        raise _capi.NfxError("image_metrics: a is %s and b is %s (the same [B, H, W, C])" % (tuple(a.shape), tuple(b.shape)))
+    if not (a.is_contiguous() and b.is_contiguous()):
+        raise _capi.NfxError("image_metrics: a and b must be contiguous")
+    B, H, W, C = (int(x) for x in a.shape)
+    max_val = float(max_val)
+    if not (max_val > 0. and max_val < float('inf')):
+        raise _capi.NfxError("image_metrics: max_val = %r (positive and finite)" % max_val)
+    if H < 11 or W < 11:
+        raise _capi.NfxError("image_metrics: images of %d x %d pixels, the 11 x 11 window needs at least 11 x 11" % (H, W))
+    if C not in (1, 3):
+        raise _capi.NfxError("image_metrics: C = %d channels (1 or 3)" % C)
+    if H * W > IMAGE_METRICS_MAX_PIXELS:
+        raise _capi.NfxError("image_metrics: %d x %d = %d pixels per image, at most %d" % (H, W, H * W, IMAGE_METRICS_MAX_PIXELS))
+    luma = bool(luma)
+    cp = 1 if (luma and C == 3) else C
+    nbytes = lib.nfx_image_metrics_workspace_bytes(B, H, W, C, int(luma))
+    if nbytes == 0:
+        raise _capi.NfxError("image_metrics: B = %d images of %d scored channels (1 <= B, B * channels <= 65535)" % (B, cp))
+    dev = a.device
+
+    def buffer(t, name, dtype, shape):
+        if t is None:
+            return torch.empty(shape, dtype=dtype, device=dev)
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+            raise _capi.NfxError("image_metrics: `%s` must be a contiguous CUDA %s tensor of shape %s" % (name, dtype, tuple(shape)))
+        return t
+
+    if mask is not None:
+        mask = buffer(mask, 'mask', torch.uint8, (B, H, W))
+    if return_map or ssim_map is not None:
+        ssim_map = buffer(ssim_map, 'ssim_map', torch.float64, (B, H - 10, W - 10, cp))
+    totals = buffer(totals, 'totals', torch.int64, (B, 8))
+    if ws is None:
+        ws = torch.empty((nbytes // 8,), dtype=torch.int64, device=dev)
+    elif not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.dtype == torch.int64 and ws.is_contiguous() and ws.numel() * 8 >= nbytes):
+        raise _capi.NfxError("image_metrics: the workspace must be a contiguous CUDA int64 tensor of at least %d words" % (nbytes // 8))
+    g = (ctypes.c_double * 11)(*IMAGE_METRICS_WEIGHTS)
+    check(lib.nfx_image_metrics(_ptr(a), _ptr(b), int(a.dtype == torch.float32), B, H, W, C, max_val, int(luma), _ptr(mask),
+                                _ptr(ssim_map), ctypes.cast(g, ctypes.c_void_p), _ptr(totals), _ptr(ws), ws.numel() * 8, _stream()),
+          'nfx_image_metrics')
+    host = totals.cpu()
+    rows = [image_metrics_finalize(r, (H - 10) * (W - 10) * cp, max_val) for r in host.tolist()]
+    out = {k: torch.tensor([r[k] for r in rows], dtype=torch.float64) for k in ('mse', 'psnr', 'ssim')}
+    out['n_px'] = torch.tensor([r['n_px'] for r in rows], dtype=torch.int64)
+    out['totals'] = host
+    out['ssim_map'] = ssim_map
+    return out
+
+
 def _shade_common(xyz, cam, normal, albedo, rough, spec, lvis, lxyz, lareas, lvis_row=None):
     xyz = _dev(xyz, 'xyz', (None, 3))
     n = xyz.shape[0]
