@@ -159,6 +159,19 @@ NFX_API int nfx_nerf_mlp_fwd_folded(const float *dev_rayo, const float *dev_rayd
                             int64_t n_rays, int n_samples, const void *dev_blob, void *dev_workspace,
                             size_t workspace_bytes, float *dev_rgbs, void *stream);
 
+/* nfx_nerf_mlp_fwd_folded with the default kernel (option nerf_variant 7) taking its tiles of
+ * 256 points from a counter on the device instead of walking them at a fixed stride: a workgroup
+ * that runs slower than the others then takes fewer tiles.  Same bits as nfx_nerf_mlp_fwd_folded;
+ * any other nerf_variant behaves exactly like it.  dev_workspace: nfx_nerf_render_workspace_bytes()
+ * = the render blob followed by a 16-byte control block (word 0: the counter), 16-byte aligned,
+ * not overlapping the blob.  Every call folds the blob and clears the control block on the stream
+ * before the render launch, so a workspace may be reused and the call may be captured and replayed.
+ * After the call word 0 holds the number of claims made (tiles + workgroups).                  */
+NFX_API size_t nfx_nerf_render_workspace_bytes(void);
+NFX_API int nfx_nerf_mlp_fwd_render(const float *dev_rayo, const float *dev_rayd, const float *dev_z,
+                            int64_t n_rays, int n_samples, const void *dev_blob, void *dev_workspace,
+                            size_t workspace_bytes, float *dev_rgbs, void *stream);
+
 /* Volumetric compositing, Model.accumulate_sigma + Model._accumulate
  * (nerf.py:184-254; util/math.py:67-68 safe_cumprod; util/img.py:76-95 alpha_blend).
  * dev_noise: NULL or N(0,1)*noise_std already scaled, [n_rays, n_samples].

@@ -51,6 +51,8 @@ SIGNATURES = {
     'nfx_nerf_fold_workspace_bytes': (_sz, []),
     'nfx_nerf_fold_blob': (_i, [_p, _p, _sz, _p]),
     'nfx_nerf_mlp_fwd_folded': (_i, [_p, _p, _p, _i64, _i, _p, _p, _sz, _p, _p]),
+    'nfx_nerf_render_workspace_bytes': (_sz, []),
+    'nfx_nerf_mlp_fwd_render': (_i, [_p, _p, _p, _i64, _i, _p, _p, _sz, _p, _p]),
     'nfx_composite_fwd': (_i, [_p, _p, _p, _p, _i64, _i, _i, _p, _p, _p, _p, _p, _p]),
     'nfx_sample_fine': (_i, [_p, _p, _i64, _i, _i, _p, _p, _p]),
     'nfx_nerf_surface_fwd': (_i, [_p, _p, _p, _p, _i64, _i, _f, _i, _p, _p, _p, _p, _p]),
@@ -169,7 +171,7 @@ def check(rc, what):
 
 
 # ------------------------------------------------------------------------------- options
-OPTION_KEYS = ('nerf_variant', 'nerf_fold', 'nerf_blocks', 'm128_blocks', 'lvis_variant', 'brdf_variant', 'brdf_ct', 'nerf_bwd',
+OPTION_KEYS = ('nerf_variant', 'nerf_fold', 'nerf_handout', 'nerf_blocks', 'm128_blocks', 'lvis_variant', 'brdf_variant', 'brdf_ct', 'nerf_bwd',
                'nerf_bwd_nw', 'm128_bwd', 'wgrad_lds', 'wgrad_slabs', 'wgrad_rounds', 'wgrad_narrow', 'wgrad_fused', 'lvis_verify', 'lvis_rows', 'brdf_bwd_rows', 'nerf_bwd_rows', 'sigma_grad_rows', 'sigma_variant',
                'sigma_x3_variant')
 

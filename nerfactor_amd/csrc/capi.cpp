@@ -50,6 +50,9 @@ Option g_options[] = {
     {"nerf_fold", {0}, {0}},      // 1 / unset: the HOST side (ops.nerf_mlp_fwd) renders bf16 through nfx_nerf_mlp_fwd_folded (bottleneck folded
                                   //    into rgb_out[0]: same density bits, rgb logits within one bf16 layer's rounding); 0 = nfx_nerf_mlp_fwd.
                                   //    The library only stores it.
+    {"nerf_handout", {0}, {0}},   // 1 / unset: the HOST side (ops.nerf_mlp_fwd) renders folded bf16 through nfx_nerf_mlp_fwd_render (variant 7 takes
+                                  //    its point tiles from a device counter: same bits); 0 = nfx_nerf_mlp_fwd_folded (static walk).  The library
+                                  //    only stores it.
     {"nerf_blocks", {0}, {0}},    // persistent grid of the NeRF kernels (default 256)
     {"m128_blocks", {0}, {0}},    // persistent grid of the width-128 kernels (default 256)
     {"lvis_variant", {0}, {0}},   // light visibility: 8 (default) | 2 | 3 | 4 | 0 — all bit-identical
@@ -208,7 +211,25 @@ int nfx_nerf_fold_blob(const void* blob, void* workspace, size_t workspace_bytes
     const uintptr_t b = (uintptr_t)blob, w = (uintptr_t)workspace;
     REQUIRE(b + nfx::nerf::kBlobBytes <= w || w + nfx_nerf_fold_workspace_bytes() <= b,
             "nfx_nerf_fold_blob: the workspace overlaps the blob");
-    return nfx_hip_result(nfx_launch_nerf_fold(blob, workspace, (hipStream_t)stream), "nerf_fold_blob");
+    return nfx_hip_result(nfx_launch_nerf_fold(blob, workspace, nullptr, (hipStream_t)stream), "nerf_fold_blob");
+}
+
+// The render launch of the two folded entry points over the render blob in `workspace`.  counter: null (static walk) or the
+// zeroed tile counter of variant 7's hand-out; every other variant ignores it.
+static int folded_render(const char* who, const float* rayo, const float* rayd, const float* z, int64_t n_rays, int n_samples,
+                         const void* workspace, unsigned* counter, float* rgbs, void* stream) {
+    const long long n_pts = (long long)n_rays * n_samples;
+    const int blocks = nfx_option_int("nerf_blocks", 256);
+    const int variant = nfx_option_int("nerf_variant", 7);   // as nfx_nerf_mlp_fwd; all bit-identical to each other
+    if (variant == 6 || variant == 7 || variant == 8)
+        return nfx_hip_result(nfx_launch_nerf_mlp_bf16_v6_fold(rayo, rayd, z, n_pts, n_samples, workspace, rgbs, blocks,
+                                                               variant == 8 ? 2 : variant == 7 ? 1 : 0, counter, (hipStream_t)stream),
+                              "nerf_mlp_fwd_folded(bf16, v6-8)");
+    if (variant != 0 && variant != 1)
+        return nfx_fail(NFX_EINVAL, "%s: NFX_NERF_VARIANT %d is not built (0, 1, 6, 7, 8)", who, variant);
+    return nfx_hip_result(nfx_launch_nerf_mlp_bf16_fold(rayo, rayd, z, n_pts, n_samples, workspace, rgbs, variant, blocks,
+                                                        (hipStream_t)stream),
+                          "nerf_mlp_fwd_folded(bf16)");
 }
 
 int nfx_nerf_mlp_fwd_folded(const float* rayo, const float* rayd, const float* z, int64_t n_rays, int n_samples,
@@ -221,18 +242,31 @@ int nfx_nerf_mlp_fwd_folded(const float* rayo, const float* rayd, const float* z
     // folded on every call, never cached: blobs are re-packed in place on the device while a network trains
     const int rc = nfx_nerf_fold_blob(blob, workspace, workspace_bytes, stream);
     if (rc) return rc;
-    const long long n_pts = (long long)n_rays * n_samples;
-    const int blocks = nfx_option_int("nerf_blocks", 256);
-    const int variant = nfx_option_int("nerf_variant", 7);   // as nfx_nerf_mlp_fwd; all bit-identical to each other
-    if (variant == 6 || variant == 7 || variant == 8)
-        return nfx_hip_result(nfx_launch_nerf_mlp_bf16_v6_fold(rayo, rayd, z, n_pts, n_samples, workspace, rgbs, blocks,
-                                                               variant == 8 ? 2 : variant == 7 ? 1 : 0, (hipStream_t)stream),
-                              "nerf_mlp_fwd_folded(bf16, v6-8)");
-    if (variant != 0 && variant != 1)
-        return nfx_fail(NFX_EINVAL, "nfx_nerf_mlp_fwd_folded: NFX_NERF_VARIANT %d is not built (0, 1, 6, 7, 8)", variant);
-    return nfx_hip_result(nfx_launch_nerf_mlp_bf16_fold(rayo, rayd, z, n_pts, n_samples, workspace, rgbs, variant, blocks,
-                                                        (hipStream_t)stream),
-                          "nerf_mlp_fwd_folded(bf16)");
+    return folded_render("nfx_nerf_mlp_fwd_folded", rayo, rayd, z, n_rays, n_samples, workspace, nullptr, rgbs, stream);
+}
+
+// ---- the same with variant 7's point tiles handed out from a device counter (nerf_mlp_v6.hip).  The workspace is the render
+// blob followed by a 16-byte control block (word 0: the counter), which the fold kernel clears on every call.
+size_t nfx_nerf_render_workspace_bytes(void) { return nfx::nerf::fold::kBlobBytes + 16; }
+
+int nfx_nerf_mlp_fwd_render(const float* rayo, const float* rayd, const float* z, int64_t n_rays, int n_samples,
+                            const void* blob, void* workspace, size_t workspace_bytes, float* rgbs, void* stream) {
+    static_assert(nfx::nerf::fold::kBlobBytes % 16 == 0, "the control block is 16-byte aligned behind the render blob");
+    REQUIRE(n_rays >= 0 && n_samples >= 1, "nfx_nerf_mlp_fwd_render: bad shape (%lld rays, %d samples)",
+            (long long)n_rays, n_samples);
+    if (n_rays == 0) return NFX_OK;
+    REQUIRE(rayo && rayd && z && blob && workspace && rgbs, "nfx_nerf_mlp_fwd_render: null pointer");
+    REQUIRE(workspace_bytes >= nfx_nerf_render_workspace_bytes(), "nfx_nerf_mlp_fwd_render: workspace too small (%zu < %zu)",
+            workspace_bytes, nfx_nerf_render_workspace_bytes());
+    if (!ALIGNED(blob, 16) || !ALIGNED(workspace, 16) || !ALIGNED(rgbs, 16))
+        return nfx_fail(NFX_EALIGN, "nfx_nerf_mlp_fwd_render: blob, workspace and rgbs must be 16-byte aligned");
+    const uintptr_t b = (uintptr_t)blob, w = (uintptr_t)workspace;
+    REQUIRE(b + nfx::nerf::kBlobBytes <= w || w + nfx_nerf_render_workspace_bytes() <= b,
+            "nfx_nerf_mlp_fwd_render: the workspace overlaps the blob");
+    void* ctrl = (char*)workspace + nfx::nerf::fold::kBlobBytes;
+    const int rc = nfx_hip_result(nfx_launch_nerf_fold(blob, workspace, ctrl, (hipStream_t)stream), "nerf_fold_blob");
+    if (rc) return rc;
+    return folded_render("nfx_nerf_mlp_fwd_render", rayo, rayd, z, n_rays, n_samples, workspace, (unsigned*)ctrl, rgbs, stream);
 }
 
 int nfx_composite_fwd(const float* rgbs, const float* z, const float* rayd, const float* noise,

@@ -112,7 +112,7 @@ size_t nfx_nerf_bwd_list_bytes(long long n_pts);
 int nfx_launch_nerf_bwd(const float* rayo, const float* rayd, const float* z, long long n_pts, int n_samples, const void* blob,
                         const float* d_rgbs, void* wsp, long long ld, int max_blocks, hipStream_t st, void* list_ws);
 // ---- nerf_fold.hip
-int nfx_launch_nerf_fold(const void* blob, void* out, hipStream_t stream);
+int nfx_launch_nerf_fold(const void* blob, void* out, void* ctrl, hipStream_t stream);
 // ---- nerf_geom.hip (the gradient launchers take the every-sample and the list form of Points, and refuse the last-sample one)
 int nfx_launch_nerf_sigma_grad(const nfx::geo::Points* pts, const void* blob, float* out, int max_blocks, hipStream_t st);
 int nfx_launch_select_density(const float* sigma, long long n_pts, float* out, void* list_ws, hipStream_t st);
@@ -130,7 +130,7 @@ int nfx_launch_nerf_mlp_bf16_fold(const float* rayo, const float* rayd, const fl
 int nfx_launch_nerf_mlp_bf16_v6(const float* rayo, const float* rayd, const float* z, long long n_pts, int n_samples, const void* blob,
                                 float* out, int max_blocks, int dma_mode, hipStream_t stream);
 int nfx_launch_nerf_mlp_bf16_v6_fold(const float* rayo, const float* rayd, const float* z, long long n_pts, int n_samples, const void* blob,
-                                     float* out, int max_blocks, int dma_mode, hipStream_t stream);
+                                     float* out, int max_blocks, int dma_mode, unsigned* counter, hipStream_t stream);
 // ---- nerf_mlp_x3.hip
 int nfx_launch_nerf_mlp_x3(const float* rayo, const float* rayd, const float* z, long long n_pts, int n_samples, const void* blob,
                            float* out, int max_blocks, hipStream_t stream);

@@ -49,8 +49,12 @@ struct Seg {
     int src, dst, n;   // 16-byte units
 };
 
-__global__ __launch_bounds__(kThreads) void nerf_fold_kernel(const char* __restrict__ blob, char* __restrict__ out) {
+// ctrl: null, or the 16-byte control block of a render workspace (nfx.h: nfx_nerf_render_workspace_bytes), cleared here so that
+// the render launch behind this one on the stream finds its tile counter at 0 on every call, replays of a captured graph included.
+__global__ __launch_bounds__(kThreads) void nerf_fold_kernel(const char* __restrict__ blob, char* __restrict__ out,
+                                                             uint4* __restrict__ ctrl) {
     using namespace nerf;
+    if (ctrl && blockIdx.x == kBiasBlock && threadIdx.x == kThreads - 1) *ctrl = make_uint4(0u, 0u, 0u, 0u);
     const uint16_t* w = reinterpret_cast<const uint16_t*>(blob);
     const float* fl = reinterpret_cast<const float*>(blob + kWeightBytes);
     const int b = blockIdx.x;
@@ -105,9 +109,10 @@ static_assert(nerf::chunk_frags(73) == 24 && nerf::chunk_frags(64) == 16, "layou
 }  // namespace nfold
 }  // namespace nfx
 
-// blob: a packed bf16 NeRF blob (nerf::kBlobBytes); out: nerf::fold::kBlobBytes, 16-byte aligned, not overlapping blob.
-extern "C" int nfx_launch_nerf_fold(const void* blob, void* out, hipStream_t stream) {
+// blob: a packed bf16 NeRF blob (nerf::kBlobBytes); out: nerf::fold::kBlobBytes, 16-byte aligned, not overlapping blob;
+// ctrl: null or 16 bytes, 16-byte aligned, that one thread clears.
+extern "C" int nfx_launch_nerf_fold(const void* blob, void* out, void* ctrl, hipStream_t stream) {
     using namespace nfx::nfold;
-    hipLaunchKernelGGL(nerf_fold_kernel, dim3(kBlocks), dim3(kThreads), 0, stream, (const char*)blob, (char*)out);
+    hipLaunchKernelGGL(nerf_fold_kernel, dim3(kBlocks), dim3(kThreads), 0, stream, (const char*)blob, (char*)out, (uint4*)ctrl);
     return (int)hipGetLastError();
 }

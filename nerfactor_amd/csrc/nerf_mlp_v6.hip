@@ -38,13 +38,37 @@ struct PointIn {
 template <int DMA, Seq S>
 __device__ __forceinline__ void nerf_mlp_bf16_v6_body(
     const float* __restrict__ rayo, const float* __restrict__ rayd, const float* __restrict__ zbuf, long long n_pts,
-    int n_samples, const char* __restrict__ blob, float4* __restrict__ out) {
+    int n_samples, const char* __restrict__ blob, float4* __restrict__ out, unsigned* __restrict__ counter) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using namespace nerf;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, p = lane & 31;
     constexpr bool FOLD = S == Seq::Render;
     constexpr bool kAhead = DMA == 1;   // fetch the next point tile's inputs one tile ahead (below)
     float* bias_lds = floats_of<DMA, S>(smem);
+    // The hand-out of point tiles (DMA == 1 with a counter; a null counter is the static walk tl, tl + gridDim.x, ...).  A
+    // workgroup's first tile is blockIdx.x; every further one is gridDim.x + fetch_add(counter, 1), relaxed at agent scope: the
+    // claim only numbers the tiles, no data passes between workgroups, so nothing is acquired or released.  Lane 0 of wave 0
+    // claims, and the index reaches the other waves through ONE LDS word behind the blob's floats (launch_v6 asks for it):
+    //   claim  the atomic of pass k is issued behind layer 0, beside the fetch-ahead loads (see there);
+    //   write  its result goes to the word between the barriers of the last two tiles of pass k (behind the last tile of
+    //          rgb_out[0], in front of rgb_out[1]), and wave 0 drains its LDS queue there (the tile barrier is a bare s_barrier).
+    //          Not at the very end of the pass, where the fetched inputs are taken over: no barrier lies between there and the read;
+    //   read   every wave reads the word at the top of pass k + 1, behind the barrier of pass k's last tile: it is the tile of
+    //          pass k + 2, whose inputs pass k + 1 fetches.  The write of pass k + 1 lies behind the barriers of that pass's
+    //          tiles 0 .. n - 2, which a wave reaches only after its read at the top of the pass (the value feeds the division
+    //          there).  The first claim is made and written in front of the prologue's __syncthreads.
+    // Depth: at the top of a pass the workgroup knows the tile it starts and the next one; behind layer 0 it claims one more.  So
+    // it holds at most TWO claimed tiles it has not started, and a launch ends with at most two passes of one workgroup to wait for.
+    // Exit: all four waves take the next index from the same word between the same two barriers, through readfirstlane, so
+    // `tl < n_tiles` is the same in every wave of the workgroup: no wave leaves a barrier behind.  A workgroup claims once
+    // in front of the loop and once per pass, two of them at or past n_tiles: the counter ends at n_tiles + gridDim.x.
+    // (tests/test_cpu_nerf_handout.py walks this protocol under every order of the atomics.)
+    bool handout = false;
+    unsigned* const next_word = reinterpret_cast<unsigned*>(smem + lds_of<DMA, S>);
+    if constexpr (kAhead) {
+        handout = counter != nullptr;
+        if (handout && tid == 0) *next_word = gridDim.x + __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     Acc accs[2];
     Pre pre;
     Regs rg;
@@ -82,14 +106,20 @@ __device__ __forceinline__ void nerf_mlp_bf16_v6_body(
         own_point(blockIdx.x, mm, ray);
         fetch(mm, ray, ahead);
     }
-    for (long long tl = blockIdx.x; tl < n_tiles; tl += gridDim.x) {
+    const bool claims = handout && cx.wave == 0;   // wave-uniform
+    for (long long tl = blockIdx.x; tl < n_tiles;) {
         bf16x8 pe[4][kCT], pv[2][kCT];
         long long m[kCT];
 #pragma unroll
         for (int c = 0; c < kCT; ++c) m[c] = tl * kTilePts + wave * (32 * kCT) + c * 32 + p;
+        long long nxt = 0;   // this workgroup's next point tile (the register-staged variants add the stride at the bottom, as ever)
+        if constexpr (kAhead) {
+            nxt = tl + gridDim.x;
+            if (handout) nxt = (unsigned)__builtin_amdgcn_readfirstlane((int)*next_word);
+        }
         // the division stays up here, outside the one basic block of the tiles; only the loads move (below)
         long long mm, ray;
-        own_point(kAhead ? tl + gridDim.x : tl, mm, ray);
+        own_point(kAhead ? nxt : tl, mm, ray);
         PointIn in;
         if constexpr (kAhead) in = ahead;
         else fetch(mm, ray, in);
@@ -110,6 +140,18 @@ __device__ __forceinline__ void nerf_mlp_bf16_v6_body(
         };
         using T = std::true_type;
         using F = std::false_type;
+        unsigned got;   // wave 0, lane 0: the claim of this pass (an AccVGPR the compiler does not know to be in flight: below)
+        // the claimed index to the LDS word, between the barriers of the pass's last two tiles (top of the function)
+        auto publish = [&] {
+            if constexpr (kAhead) {
+                if (claims && lane == 0) {
+                    // volatile like the tiles' barriers, so it stays behind them: `got` is not read before this statement
+                    asm volatile("" : "+a"(got));
+                    *next_word = gridDim.x + got;
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                }
+            }
+        };
         // chunk index K: L0 0-7, L1-4 8-39, L5 40-47, L6-7 48-63, bottleneck 64-71, sigma 72, rgb0 73-76, rgb1 77
         // (folded: sigma 64, rgb0 65-68, rgb1 69); tile K accumulates in accs[K & 1]
         layer<0, 4, 0, 8, true, DMA, S>(cx, rg, bl, bl + 256 * 1, pe, pe, ha, accs, pre, EpiNone{});
@@ -118,6 +160,20 @@ __device__ __forceinline__ void nerf_mlp_bf16_v6_body(
             // issue order, so the next counted wait of tile<> (end of tile 8) also waits for them — it is a full 16-k-step tile
             // away.  (The waits can only wait for more with older loads in flight: they stay correct.)  The empty statement
             // keeps the compiler from issuing the loads at the loop top, in front of tile 0's wait.
+            // The claim of wave 0 is one more such load, and the same argument holds: a returning atomic counts in vmcnt in issue
+            // order with the pieces, so behind it a counted wait of tile<> can only wait for more — and the wait that ends tile 8
+            // leaves only that tile's own pieces in flight, so the claim has landed 60 tiles before publish() reads it.
+            // Written as one statement with the result in an AccVGPR: given the builtin, the compiler parks the result in an
+            // AccVGPR itself, behind an s_waitcnt vmcnt(0) right here that waits for the atomic and every piece in flight (the
+            // VGPRs are full), and wraps the atomic in a wave reduction.  EXEC is 1 in the claiming wave and 0 in all others, the
+            // static walk included: no branch splits the block of the tiles, and a wave with EXEC = 0 touches no memory.
+            unsigned long long exec_saved;
+            const unsigned claim_exec = __builtin_amdgcn_readfirstlane((unsigned)claims);   // a scalar register, by construction
+            asm volatile("s_mov_b64 %1, exec\n\ts_mov_b32 exec_lo, %2\n\ts_mov_b32 exec_hi, 0\n\t"
+                         "global_atomic_add %0, %3, %4, %5 sc0\n\ts_mov_b64 exec, %1"
+                         : "=&a"(got), "=&s"(exec_saved)
+                         : "s"(claim_exec), "v"(0u), "a"(1u), "s"(counter)
+                         : "memory");
             asm volatile("" : "+v"(mm), "+v"(ray));
             fetch(mm, ray, ahead);
         }
@@ -137,6 +193,7 @@ __device__ __forceinline__ void nerf_mlp_bf16_v6_body(
             EpiSigma es{accs[0], sigma};
             layer<65, 16, 2, 4, true, DMA, S>(cx, rg, bias_lds + kBiasRgb0, bias_lds + kBiasRgb1, hb, pv, r0, accs, pre, es);
         }
+        publish();
         // rgb_out[1] (K = 69 -> accs[1]); pending: last rgb_out[0] tile (K = 68 -> accs[0]); next: L0 tile 0
         tile<69, 8, 0, DMA, S>(cx, rg, bl, r0, pe, accs[1], accs[0], pre, pend(T{}, accs[0], r0[6], r0[7]));
         } else {
@@ -150,6 +207,7 @@ __device__ __forceinline__ void nerf_mlp_bf16_v6_body(
             EpiSigma es{accs[0], sigma};
             layer<73, 16, 2, 4, true, DMA, S>(cx, rg, bias_lds + kBiasRgb0, bias_lds + kBiasRgb1, ha, pv, r0, accs, pre, es);
         }
+        publish();
         // rgb_out[1] (K = 77 -> accs[1]); pending: last rgb_out[0] tile (K = 76 -> accs[0]); next: L0 tile 0
         tile<77, 8, 0, DMA, S>(cx, rg, bl, r0, pe, accs[1], accs[0], pre, pend(T{}, accs[0], r0[6], r0[7]));
         }
@@ -164,6 +222,7 @@ __device__ __forceinline__ void nerf_mlp_bf16_v6_body(
             for (int c = 0; c < kCT; ++c)
                 if (m[c] < n_pts) out[m[c]] = make_float4(accs[1].v[c][0], accs[1].v[c][1], accs[1].v[c][2], sigma[c]);
         }
+        tl = kAhead ? nxt : tl + gridDim.x;
     }
 }
 
@@ -172,29 +231,35 @@ __device__ __forceinline__ void nerf_mlp_bf16_v6_body(
 template <int AB, int DMA>
 __global__ __launch_bounds__(kNW * 64, 1) void nerf_mlp_bf16_v6_kernel(
     const float* __restrict__ rayo, const float* __restrict__ rayd, const float* __restrict__ zbuf, long long n_pts,
-    int n_samples, const char* __restrict__ blob, float4* __restrict__ out) {
-    nerf_mlp_bf16_v6_body<DMA, Seq::Packed>(rayo, rayd, zbuf, n_pts, n_samples, blob, out);
+    int n_samples, const char* __restrict__ blob, float4* __restrict__ out, unsigned* __restrict__ counter) {
+    nerf_mlp_bf16_v6_body<DMA, Seq::Packed>(rayo, rayd, zbuf, n_pts, n_samples, blob, out, counter);
 }
 
 namespace fold {   // over a render blob: 70 tiles
 template <int AB, int DMA>
 __global__ __launch_bounds__(kNW * 64, 1) void nerf_mlp_bf16_v6_kernel(
     const float* __restrict__ rayo, const float* __restrict__ rayd, const float* __restrict__ zbuf, long long n_pts,
-    int n_samples, const char* __restrict__ blob, float4* __restrict__ out) {
-    nerf_mlp_bf16_v6_body<DMA, Seq::Render>(rayo, rayd, zbuf, n_pts, n_samples, blob, out);
+    int n_samples, const char* __restrict__ blob, float4* __restrict__ out, unsigned* __restrict__ counter) {
+    nerf_mlp_bf16_v6_body<DMA, Seq::Render>(rayo, rayd, zbuf, n_pts, n_samples, blob, out, counter);
 }
 }  // namespace fold
 
 }  // namespace v6
 }  // namespace nfx
 
+// counter: null (the static walk) or a zeroed 32-bit word in global memory, DMA == 1 only: tiles handed out (the body's comment).
+// The index word rides behind the blob's floats in LDS; a tile count the 32-bit index cannot hold walks statically.
 template <int DMA, bool FOLD>
 static int launch_v6(const float* rayo, const float* rayd, const float* z, long long n_pts, int n_samples,
-                     const void* blob, float* out, int max_blocks, hipStream_t stream) {
+                     const void* blob, float* out, int max_blocks, hipStream_t stream, unsigned* counter = nullptr) {
     using namespace nfx;
     auto kern = FOLD ? v6::fold::nerf_mlp_bf16_v6_kernel<0, DMA> : v6::nerf_mlp_bf16_v6_kernel<0, DMA>;
     constexpr int lds = v6::lds_of<DMA, FOLD ? v6::Seq::Render : v6::Seq::Packed>;
-    return v6::launch_tiles(kern, lds, n_pts, max_blocks, stream, rayo, rayd, z, n_pts, n_samples, (const char*)blob, (float4*)out);
+    static_assert(lds % 4 == 0 && lds + 16 <= 160 * 1024, "room for the hand-out's index word");
+    const long long n_tiles = (n_pts + v6::kTilePts - 1) / v6::kTilePts;
+    if (DMA != 1 || n_tiles >= (1ll << 31) - max_blocks) counter = nullptr;
+    return v6::launch_tiles(kern, counter ? lds + 16 : lds, n_pts, max_blocks, stream, rayo, rayd, z, n_pts, n_samples,
+                            (const char*)blob, (float4*)out, counter);
 }
 
 extern "C" int nfx_launch_nerf_mlp_bf16_v6(const float* rayo, const float* rayd, const float* z, long long n_pts,
@@ -206,12 +271,13 @@ extern "C" int nfx_launch_nerf_mlp_bf16_v6(const float* rayo, const float* rayd,
     return launch_v6<0, false>(rayo, rayd, z, n_pts, n_samples, blob, out, max_blocks, stream);                      // variant 6
 }
 
-// The same three variants over a RENDER blob (nerf_fold.hip): 70 tiles, the bottleneck folded into rgb_out[0].
+// The same three variants over a RENDER blob (nerf_fold.hip): 70 tiles, the bottleneck folded into rgb_out[0].  `counter`
+// (variant 7 only, else ignored): see launch_v6.
 extern "C" int nfx_launch_nerf_mlp_bf16_v6_fold(const float* rayo, const float* rayd, const float* z, long long n_pts,
                                                 int n_samples, const void* blob, float* out, int max_blocks, int dma_mode,
-                                                hipStream_t stream) {
+                                                unsigned* counter, hipStream_t stream) {
     if (n_pts <= 0) return 0;
-    if (dma_mode == 1) return launch_v6<1, true>(rayo, rayd, z, n_pts, n_samples, blob, out, max_blocks, stream);
+    if (dma_mode == 1) return launch_v6<1, true>(rayo, rayd, z, n_pts, n_samples, blob, out, max_blocks, stream, counter);
     if (dma_mode == 2) return launch_v6<2, true>(rayo, rayd, z, n_pts, n_samples, blob, out, max_blocks, stream);
     return launch_v6<0, true>(rayo, rayd, z, n_pts, n_samples, blob, out, max_blocks, stream);
 }

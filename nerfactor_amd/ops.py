@@ -319,6 +319,13 @@ def nerf_mlp_fwd(rayo, rayd, z, blob, prec='bf16', fold=None):
         # the render blob is re-made on every call (blobs are re-packed in place during training, a cache keyed on the
         # address could go stale); the workspace comes from torch's caching allocator: no host synchronisation, safe
         # under stream capture
+        # option nerf_handout (on unless set to 0): the default kernel takes its point tiles from a device counter in the
+        # workspace's control block, which the fold clears on every call (csrc/nerf_mlp_v6.hip; same bits)
+        if _capi.get_option('nerf_handout') != 0:
+            ws = torch.empty(lib.nfx_nerf_render_workspace_bytes(), dtype=torch.uint8, device=z.device)
+            check(lib.nfx_nerf_mlp_fwd_render(_ptr(rayo), _ptr(rayd), _ptr(z), n, s, _ptr(blob), _ptr(ws), ws.numel(),
+                                              _ptr(out), _stream()), 'nfx_nerf_mlp_fwd_render')
+            return out
         ws = torch.empty(lib.nfx_nerf_fold_workspace_bytes(), dtype=torch.uint8, device=z.device)
         check(lib.nfx_nerf_mlp_fwd_folded(_ptr(rayo), _ptr(rayd), _ptr(z), n, s, _ptr(blob), _ptr(ws), ws.numel(),
                                           _ptr(out), _stream()), 'nfx_nerf_mlp_fwd_folded')
