@@ -453,6 +453,42 @@ NFX_API int nfx_image_metrics(const void *dev_a, const void *dev_b, int is_float
                               const double *host_weights, int64_t *dev_totals, void *dev_workspace,
                               size_t workspace_bytes, void *stream);
 
+/* Antialiased bilinear resize of a batch of channels-last images, tf.image.resize(bilinear, antialias=True)
+ * (csrc/resize.hip).
+ *   Table     of one axis, a function of (n_in, n_out) only, all in fp64 without fused multiply-adds: scale = n_in / n_out,
+ *             support = max(scale, 1); output i has centre (i + 0.5) scale; tap x has weight max(0, 1 - |(x + 0.5) - centre| /
+ *             support); the taps of output i are the contiguous run of x in [0, n_in) with weight > 0: first[i], count[i];
+ *             their sum s is taken in ascending x, starting from the first weight; weights[i max_taps + k] =
+ *             (float)(weight(first[i] + k) / s), entries k >= count[i] are written as 0.  count[i] <= ceil(2 support) + 1.
+ *             nfx_resize_axis_table is host only (no GPU call); it returns the largest count[i], or a negative NFX_E* code;
+ *             with first = count = weights = null it only returns that count (max_taps is then not read).
+ *   Images    dev_in [batch, h, w, c] contiguous, in_type NFX_RESIZE_U8 | _U16 | _F32; an integer value v enters as
+ *             (float)v * in_scale (one float32 multiply), a float32 value as it is.  dev_out [batch, oh, ow, c] float32, or
+ *             uint8 with out_uint8 != 0: (uint8)(fminf(fmaxf(v, 0), 1) * 255.f), the multiply in float32, truncated.
+ *   Passes    horizontal first: m[y, i, ch] = sum over k of wx[i, k] * x[y, first_x[i] + k, ch], then vertical:
+ *             out[j, i, ch] = sum over k of wy[j, k] * m[first_y[j] + k, i, ch].  Each sum starts at t = 0 and takes
+ *             t = t + w[k] * x[k] in ascending k, float32, the multiply and the add rounded separately; m is float32.
+ *             One thread computes one output value, so the result has the same bits for every launch shape and on every
+ *             run, whatever dev_out held before.
+ *   Tables    dev_first_*, dev_count_* (int32 [n_out]) and dev_weights_* (float32 [n_out, taps_*]) in device memory, as
+ *             nfx_resize_axis_table fills them with max_taps = taps_*: y for (h, oh), x for (w, ow).
+ *   Limits    1 <= batch <= 65535; 1 <= h, w, oh, ow <= NFX_RESIZE_MAX_SIDE; h <= 16 oh and w <= 16 ow (at most
+ *             NFX_RESIZE_MAX_TAPS taps per axis; any magnification); 1 <= taps_* <= NFX_RESIZE_MAX_TAPS; 1 <= c <=
+ *             NFX_RESIZE_MAX_CHANNELS; at most 2^31 - 1 tiles per image; refused with their numbers before anything is launched.
+ *   Work      one workgroup per tile of output pixels and chunk of channels; it stages the tile's input footprint in
+ *             LDS in the input's type and does both passes from there.  Nothing allocated, no synchronisation with the host. */
+#define NFX_RESIZE_U8 0
+#define NFX_RESIZE_U16 1
+#define NFX_RESIZE_F32 2
+#define NFX_RESIZE_MAX_TAPS 33
+#define NFX_RESIZE_MAX_SIDE 65536
+#define NFX_RESIZE_MAX_CHANNELS 4096
+NFX_API int nfx_resize_axis_table(int n_in, int n_out, int32_t *first, int32_t *count, float *weights, int max_taps);
+NFX_API int nfx_resize_antialias(const void *dev_in, int in_type, int64_t batch, int h, int w, int c, float in_scale,
+                                 const int32_t *dev_first_y, const int32_t *dev_count_y, const float *dev_weights_y, int taps_y,
+                                 const int32_t *dev_first_x, const int32_t *dev_count_x, const float *dev_weights_x, int taps_x,
+                                 void *dev_out, int out_uint8, int oh, int ow, void *stream);
+
 /* Rusinkiewicz coordinates (phi_d, theta_h, theta_d), util/geom.py:152-192. a,b [n,3]. */
 NFX_API int nfx_dir2rusink(const float *dev_a, const float *dev_b, int64_t n, float *dev_rusink,
                    void *stream);

@@ -79,6 +79,8 @@ SIGNATURES = {
     'nfx_mesh_components': (_i, [_p, _i64, _i64, _p, _p, _sz, _p]),
     'nfx_image_metrics_workspace_bytes': (_sz, [_i64, _i, _i, _i, _i]),
     'nfx_image_metrics': (_i, [_p, _p, _i, _i64, _i, _i, _i, _d, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    'nfx_resize_axis_table': (_i, [_i, _i, _p, _p, _p, _i]),
+    'nfx_resize_antialias': (_i, [_p, _i, _i64, _i, _i, _i, _f, _p, _p, _p, _i, _p, _p, _p, _i, _p, _i, _i, _i, _p]),
     'nfx_dir2rusink': (_i, [_p, _p, _i64, _p, _p]),
     'nfx_mlp128_train_packed_bytes': (_sz, [_i]),
     'nfx_mlp128_pack_train_weights': (_i, [_pp, _pp, _i, _i, _i, _p, _sz]),

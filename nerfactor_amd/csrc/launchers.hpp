@@ -59,6 +59,10 @@ int nfx_launch_mesh_components(const int* faces, long long nf, long long nv, int
 int nfx_launch_image_metrics(const void* a, const void* b, int is_float, int batch, int h, int w, int c, int cp, double max_val,
                              const unsigned char* mask, double* ssim_map, const double* host_weights, long long* totals,
                              long long* partial, hipStream_t st);
+// ---- resize.hip (in_type: NFX_RESIZE_*; the tables: include/nfx.h; NFX_EINVAL when an image has more than 2^31 - 1 tiles)
+int nfx_launch_resize_antialias(const void* in, int in_type, int batch, int h, int w, int c, float in_scale, const int* first_y,
+                                const int* count_y, const float* weights_y, int taps_y, const int* first_x, const int* count_x,
+                                const float* weights_x, int taps_x, void* out, int out_uint8, int oh, int ow, hipStream_t st);
 // ---- loss.hip
 int nfx_launch_pair_loss(int bwd, const nfx_loss_term* terms, int n_terms, const float* alpha, float bg, long long n, float* loss,
                          const float* dloss, hipStream_t st);

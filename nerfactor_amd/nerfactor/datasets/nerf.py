@@ -33,6 +33,19 @@ def resize(arr, new_h):
     return np.stack(out, -1).reshape((new_h, new_w) + arr.shape[2:])
 
 
+def resize_on_device(arr, new_h):
+    """resize() at the same output size through the GPU's antialiased filter (ops.resize_antialias, DESIGN.md section 3.13;
+    ini key resize_on_device): one upload, one launch and one download per array, all channels at once."""
+    import torch
+
+    from ... import ops
+    h, w = arr.shape[:2]
+    new_w = int(round(new_h / h * w))
+    x = torch.from_numpy(np.ascontiguousarray(arr.reshape(h, w, -1), dtype=np.float32)).cuda()
+    out = ops.resize_antialias(x, new_h=new_h, new_w=new_w).cpu().numpy()
+    return out.reshape((new_h, new_w) + arr.shape[2:])
+
+
 def gen_rays(to_world, angle_x, imh, imw, sps=1):
     """Pin-hole rays through the top-left corner of every (sub)pixel, camera looking down -z (reference
     datasets/nerf.py:172-193, ndc=False).  float64 [imh sps, imw sps, 3] origins and (un-normalised) directions."""

@@ -7,7 +7,7 @@ from os.path import dirname, exists, join
 
 import numpy as np
 
-from .nerf import Dataset as NeRFDataset, load_rgba, resize
+from .nerf import Dataset as NeRFDataset, load_rgba, resize, resize_on_device
 
 
 
@@ -73,7 +73,9 @@ class Dataset(NeRFDataset):
         if alpha.ndim == 3:
             alpha = alpha[:, :, 0]
         if imh != xyz.shape[0]:
-            xyz, normal, lvis, alpha, rgb = (resize(a, imh) for a in (xyz, normal, lvis, alpha, rgb))
+            # resize_on_device (opt-in): the GPU's antialiased filter on whole buffers, not the host's loop over channels
+            shrink = resize_on_device if cfg.getboolean('DEFAULT', 'resize_on_device', fallback=False) else resize
+            xyz, normal, lvis, alpha, rgb = (shrink(a, imh) for a in (xyz, normal, lvis, alpha, rgb))
         if rayo.shape[0] != xyz.shape[0]:       # rays at the metadata's resolution, buffers at imh (MVS views)
             rayo, rayd = resize(rayo, xyz.shape[0]), resize(rayd, xyz.shape[0])
         if np.isclose(xyz, rayo).all(axis=2).any():

@@ -1110,6 +1110,91 @@ def image_metrics(a, b, max_val, luma=True, mask=None, return_map=False, totals=
     return out
 
 
+# ------------------------------------------------------------------------- antialiased resize
+RESIZE_MAX_TAPS = 33                             # NFX_RESIZE_MAX_TAPS: an axis shrinks by at most 16
+RESIZE_MAX_CHANNELS = 4096                       # NFX_RESIZE_MAX_CHANNELS
+_RESIZE_TYPES = {torch.uint8: 0, torch.uint16: 1, torch.float32: 2}
+_resize_tables = {}
+
+
+def resize_axis_table(n_in, n_out):
+    """One axis of tf.image.resize(bilinear, antialias=True) from the host function nfx_resize_axis_table (no GPU):
+    (first int32 [n_out], count int32 [n_out], weights float32 [n_out, taps]) as NumPy arrays, taps = the largest count."""
+    n_in, n_out = int(n_in), int(n_out)
+    taps = lib.nfx_resize_axis_table(n_in, n_out, None, None, None, 0)
+    if taps < 0:
+        raise _capi.NfxError("nfx_resize_axis_table failed (%d): %s" % (taps, _capi.last_error()))
+    first, count = np.empty(n_out, np.int32), np.empty(n_out, np.int32)
+    weights = np.empty((n_out, taps), np.float32)
+    rc = lib.nfx_resize_axis_table(n_in, n_out, first.ctypes.data_as(ctypes.c_void_p), count.ctypes.data_as(ctypes.c_void_p),
+                                   weights.ctypes.data_as(ctypes.c_void_p), taps)
+    if rc != taps:
+        raise _capi.NfxError("nfx_resize_axis_table failed (%d): %s" % (rc, _capi.last_error()))
+    return first, count, weights
+
+
+def _resize_device_table(n_in, n_out, dev):
+    key = (int(n_in), int(n_out), str(dev))
+    if key not in _resize_tables:
+        if len(_resize_tables) >= 64:
+            _resize_tables.clear()
+        _resize_tables[key] = tuple(torch.from_numpy(a).to(dev) for a in resize_axis_table(n_in, n_out))
+    return _resize_tables[key]
+
+
+def resize_antialias(x, new_h=None, new_w=None, out_uint8=False, out=None):
+    """tf.image.resize(bilinear, antialias=True) of channels-last images on the GPU (nfx_resize_antialias; the arithmetic is
+    stated in include/nfx.h).  x: contiguous CUDA tensor [B, H, W, C] or [H, W, C], uint8, uint16 or float32; integer
+    values enter as float32(v) * (1 / 255) or (1 / 65535), the product rounded to float32.  When only one of new_h / new_w is
+    given the other is int(h / w * new_w) / int(w / h * new_h) as in util.light.resize_antialias.  -> float32 of the same
+    rank, or uint8 with out_uint8: (uint8)(clip(v, 0, 1) * 255), truncated.  The axis tables are built once per (n_in,
+    n_out, device) by the host function and kept on the device; `out` may be passed in, what it holds does not matter."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda):
+        raise _capi.NfxError("resize_antialias: x must be a CUDA/ROCm tensor (libnfx has no CPU path)")
+    if x.dtype not in _RESIZE_TYPES:
+        raise _capi.NfxError("resize_antialias: x is %s (uint8, uint16 or float32)" % x.dtype)
+    if x.dim() not in (3, 4):
+        raise _capi.NfxError("resize_antialias: x is %s ([B, H, W, C] or [H, W, C])" % (tuple(x.shape),))
+    if not x.is_contiguous():
+        raise _capi.NfxError("resize_antialias: x must be contiguous")
+    x4 = x if x.dim() == 4 else x[None]
+    B, H, W, C = (int(v) for v in x4.shape)
+    if min(B, H, W, C) < 1:
+        raise _capi.NfxError("resize_antialias: x is %s, every size must be at least 1" % (tuple(x.shape),))
+    if new_h is None and new_w is None:
+        raise _capi.NfxError("resize_antialias: at least one of new_h and new_w must be given")
+    if new_h is None:
+        new_h = int(H / W * new_w)
+    if new_w is None:
+        new_w = int(W / H * new_h)
+    new_h, new_w = int(new_h), int(new_w)
+    if new_h < 1 or new_w < 1:
+        raise _capi.NfxError("resize_antialias: %d x %d -> %d x %d pixels, every size must be at least 1" % (H, W, new_h, new_w))
+    if H > 16 * new_h or W > 16 * new_w:
+        raise _capi.NfxError("resize_antialias: %d x %d -> %d x %d shrinks an axis by more than 16 (more than %d taps)"
+                             % (H, W, new_h, new_w, RESIZE_MAX_TAPS))
+    if C > RESIZE_MAX_CHANNELS:
+        raise _capi.NfxError("resize_antialias: C = %d channels (1 .. %d)" % (C, RESIZE_MAX_CHANNELS))
+    out_dtype = torch.uint8 if out_uint8 else torch.float32
+    shape = (B, new_h, new_w, C)
+    if out is None:
+        out4 = torch.empty(shape, dtype=out_dtype, device=x.device)
+    else:
+        want = shape if x.dim() == 4 else shape[1:]
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == out_dtype and out.is_contiguous() and tuple(out.shape) == want):
+            raise _capi.NfxError("resize_antialias: `out` must be a contiguous CUDA %s tensor of shape %s" % (out_dtype, want))
+        out4 = out
+    fy, cy, wy = _resize_device_table(H, new_h, x.device)
+    fx, cx, wx = _resize_device_table(W, new_w, x.device)
+    in_scale = {torch.uint8: 1. / 255., torch.uint16: 1. / 65535., torch.float32: 1.}[x.dtype]
+    check(lib.nfx_resize_antialias(_ptr(x4), _RESIZE_TYPES[x.dtype], B, H, W, C, in_scale, _ptr(fy), _ptr(cy), _ptr(wy), int(wy.shape[1]),
+                                   _ptr(fx), _ptr(cx), _ptr(wx), int(wx.shape[1]), _ptr(out4), int(bool(out_uint8)), new_h, new_w,
+                                   _stream()), 'nfx_resize_antialias')
+    if out is not None:
+        return out
+    return out4 if x.dim() == 4 else out4[0]
+
+
 def _shade_common(xyz, cam, normal, albedo, rough, spec, lvis, lxyz, lareas, lvis_row=None):
     xyz = _dev(xyz, 'xyz', (None, 3))
     n = xyz.shape[0]
