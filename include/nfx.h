@@ -635,26 +635,40 @@ NFX_API int nfx_pack_gather(const float *dev_src, const int32_t *dev_map, int64_
 
 /* tf.keras.optimizers.Adam(amsgrad=True) dense update on flat fp32 buffers (trainvali.py:116-127):
  * lr_t = lr * sqrt(1 - beta2^step) / (1 - beta1^step); m, v, vhat updated in place;
- * p -= lr_t * m / (sqrt(vhat) + eps).  `step` is 1-based.                                      */
+ * p -= lr_t * m / (sqrt(vhat) + eps).  `step` is 1-based.
+ * Operation order, all float32 (what tests/step_kernel_cases.py restates and tests/test_gpu_step_kernels.py holds the
+ * kernels to bit for bit): m = m * beta1 + g * (1 - beta1); v = v * beta2 + (g * g) * (1 - beta2); vhat = max(vhat, v);
+ * p = p - (lr_t * m) / (sqrt(vhat) + eps), with a correctly rounded quotient and square root and denormals kept.
+ * lr_t = nfx_amsgrad_step_size: evaluated in DOUBLE from the float32 lr and betas (pow, sqrt, the quotient) and rounded
+ * to float32 once.  TensorFlow evaluates the same formula in float32 throughout; the two differ by up to 54 float32
+ * steps at step 2 (measured for steps 1 ... 10^6 at lr = 5e-3 and 5e-4; 0 from step 1000 on): a deliberate difference. */
 NFX_API int nfx_amsgrad_step(float *dev_p, const float *dev_g, float *dev_m, float *dev_v, float *dev_vhat,
                      int64_t n, float lr, float beta1, float beta2, float eps, int64_t step,
                      void *stream);
 /* The same update with lr_t read from device memory (dev_lr_t[0] = nfx_amsgrad_step_size(lr, beta1, beta2, step),
  * written by the host before the launch): a training step captured in a hipGraph replays with the step size of the
- * current step, not the one of the step it was captured at (nerfactor_amd/optim.py:GraphedTrainStep).            */
+ * current step, not the one of the step it was captured at (nerfactor_amd/optim.py:GraphedTrainStep).  The same
+ * arithmetic on the same word: bit-identical to nfx_amsgrad_step.                                                  */
 NFX_API float nfx_amsgrad_step_size(float lr, float beta1, float beta2, int64_t step);
 NFX_API int nfx_amsgrad_step_dev(float *dev_p, const float *dev_g, float *dev_m, float *dev_v, float *dev_vhat,
                          int64_t n, const float *dev_lr_t, float beta1, float beta2, float eps, void *stream);
 
 /* tf.linalg.l2_normalize over the rows of x[n, d] (d <= 16; util/math.py:63-64 of the reference: x * rsqrt(max(sum x^2, eps)))
  * and its pull-back dx = (d y / d x)^T dy — the predicted normals and BRDF codes of a NeRFactor training step
- * (nerfactor.py:205-206, 266-270), one launch each way instead of 5 + 12 elementwise ones.                       */
+ * (nerfactor.py:205-206, 266-270), one launch each way instead of 5 + 12 elementwise ones.
+ * Operation order, all float32: sq = ((x[0]^2 + x[1]^2) + ...) summed in column order; inv = 1 / sqrt(max(sq, eps));
+ * y = x * inv.  Pull-back: dot = the sum of x[k] * dy[k] in column order; c = ((dot * inv) * inv) * inv where
+ * sq >= eps and 0 where sq < eps (AT sq == eps the norm passes its gradient, as tf.maximum does); dx = dy * inv - x * c. */
 NFX_API int nfx_l2_normalize_rows(const float *dev_x, float *dev_y, int64_t n, int d, float eps, void *stream);
 NFX_API int nfx_l2_normalize_rows_bwd(const float *dev_x, const float *dev_dy, float *dev_dx, int64_t n, int d, float eps,
                                       void *stream);
 /* The light probe's smoothness penalties (nerfactor.py:526-539): dev_loss[0] = tv_weight * sum((L - roll(L, 1, 1))^2 +
  * (L - roll(L, 1, 0))^2) + achro_weight * sum((L - roll(L, 1, 2))^2) over dev_light[h, w, 3], and dev_grad[h, w, 3] =
- * d loss / d L.  One block, fixed reduction order.                                                                */
+ * d loss / d L.  One block, fixed reduction order: element e = (h, w, c) contributes
+ * tv_weight * (dx * dx + dy * dy) + achro_weight * (dc * dc); thread t of 256 adds elements t, t + 256, ... in order; a tree
+ * then adds part[t] += part[t + k] for k = 128, 64, ..., 1.  dev_grad[e] = 2 * (tv_weight * ((dx - (next_w - L)) +
+ * (dy - (next_h - L))) + achro_weight * (dc - (next_c - L))), neighbours wrapping around (for w = 2 or h = 2 the previous
+ * and the next neighbour are one texel).  h, w >= 1 and h * w <= 2^20.                                              */
 NFX_API int nfx_light_smoothness(const float *dev_light, int h, int w, float tv_weight, float achro_weight, float *dev_loss,
                                  float *dev_grad, void *stream);
 
@@ -662,7 +676,13 @@ NFX_API int nfx_light_smoothness(const float *dev_light, int h, int w, float tv_
  * launch: loss[ray] = sum_t w_t * mean_d f_t(A_t[ray, d] - B_t[ray, d]), f = square (keras MSE) or abs (MAE), A / B
  * optionally alpha-blended onto the background first (util/img.py:alpha_blend: x * alpha + bg * (1 - alpha)).
  * nfx_pair_loss_bwd: given dev_dloss[n] writes d loss / d A into term.ga and d loss / d B into term.gb where those
- * are non-NULL (NFX_LOSS_ACCUM_*: add to what an earlier term of the SAME call wrote — a tensor used in two terms). */
+ * are non-NULL (NFX_LOSS_ACCUM_*: add to what an earlier term of the SAME call wrote — a tensor used in two terms).
+ * Operation order, all float32 (one wave of 64 lanes per ray): blend = x * alpha + bg * (1 - alpha) (alpha = 1 without
+ * dev_alpha); lane l adds f(A - B) of elements l, l + 64, ... in order; the 64 lane sums meet in an xor butterfly over
+ * the offsets 32, 16, 8, 4, 2, 1; loss += w * (s / (float)d) in term order.  Backward: c = (dloss * w) / (float)d;
+ * g = c * (2 * diff) (MSE) or c * sign(diff) with sign(0) = 0 (MAE); ga gets g, or g * alpha where A is blended; gb gets
+ * -g, or (-g) * alpha; written, or with NFX_LOSS_ACCUM_* added to the buffer's content, in term order.  A NULL ga / gb is
+ * skipped and nothing else of that tensor is touched.  1 .. NFX_LOSS_MAX_TERMS terms, d >= 1; n = 0 launches nothing. */
 #define NFX_LOSS_MAX_TERMS 8
 #define NFX_LOSS_MSE 0
 #define NFX_LOSS_MAE 1
@@ -833,7 +853,12 @@ NFX_API int nfx_mlp_generic_bwd(const float *dev_x, int64_t n, int ld_x, int d_i
  *   mode 0: v = x[row / per_ray]        mode 1: v = x[row / per_ray] + dir[row / per_ray] * z[row]  (points along rays,
  *   nerfactor/models/nerf.py:162-164)    mode 2: v = dir[row / per_ray]
  *   mode 3: v = safe_l2_normalize(dir[row % per_ray] - x[row / per_ray]): the unit direction from surface point
- *   row / per_ray to light row % per_ray (nerfactor/models/shape.py:128-131; per_ray = number of lights). */
+ *   row / per_ray to light row % per_ray (nerfactor/models/shape.py:128-131; per_ray = number of lights).
+ * Operation order, all float32: mode 1 multiplies, then adds (no fused multiply-add); mode 3 takes
+ * v = dir - x, sq = (v0 * v0 + v1 * v1) + v2 * v2, v *= 1 / sqrt(max(sq, 1e-6f)) (a light ON the point gives the zero
+ * vector); 2^k v is exact; sine and cosine are csrc/nfx_common.hpp:sincos_cw (Cody-Waite reduction and polynomials by
+ * fmaf).  Exactly columns col0 ... col0 + 3 incl_input + 6 n_freqs - 1 of every row are written.  The pull-back:
+ * g = d[identity block] (or 0), then g += 2^k * (cos(2^k v) * d[sin block] - sin(2^k v) * d[cos block]) band by band. */
 /* The embedding's pull-back for explicit vectors (mode 0): dv[n, 3] = (d embedding / d v)^T d_out[row, col0 ...] — with
  * nfx_mlp_generic_bwd's dx it gives d(network output)/d(point), the density gradient geometry_from_nerf.py:288-297 takes
  * by tf.GradientTape, for a NeRF of any shape. */

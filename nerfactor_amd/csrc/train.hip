@@ -101,7 +101,8 @@ __global__ void amsgrad_dev_kernel(float* __restrict__ p, const float* __restric
 
 // One wave owns a [<=128 x <=128] block of dW (grid y, z) and a slab of rows (grid x).
 //   xt: [k_in][ld] bf16 (feature-major), zt: [n_out][ld] bf16; rows in [row0, row1), multiple of 16.
-//   dW: [k_in][n_out] fp32 (Keras layout), accumulated with atomics.
+//   dW: [k_in][n_out] fp32 (Keras layout); the block's partial sum goes to its own slice of `part` with plain stores and
+//   wgrad_reduce_kernel adds the slabs in slab order (no atomics: see the top of this namespace).
 constexpr int kWgTiles = 4;  // 4 x 4 tiles of 32 x 32
 __global__ __launch_bounds__(64, 1) void wgrad_kernel(WgBatch bt) {
     const int lane = threadIdx.x, h = lane >> 5, q = lane & 31;
